@@ -2,7 +2,7 @@
 (3x32x32) per MI355X — BASELINE.json's metric on configs[2] (N=1) and
 configs[3] (batch 8192 = 8 x 1024 sharded, RCCL all-gather of logits, N=8).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 A step = one forward of the whole int8 net over this rank's 1024 resident
@@ -12,10 +12,16 @@ GPU.  Weights: random-init SimpleConvNet with BN statistics recalibrated on
 synthetic CIFAR-normalised images (no trained checkpoint or dataset offline),
 calibrated once on rank 0 and broadcast.
 
-Prints ONE JSON line on rank 0 with value (whole-job images/sec), a
-``roofline`` object for the dominant kernel (HIP-event per-kernel timing over
-a second timed pass) and, at N = 1, ``cpu_baseline`` (the reference's
-StaticPTQModel path — torch.ao quantize_dynamic — timed on the host cores).
+Prints ONE JSON line on rank 0 with value (whole-job images/sec) and
+ms_per_step over the K timed steps.  A plain run does only that: set up, warm
+up, time the K steps, print.  ``--dump-outputs DIR`` also writes the logits of
+the last timed step to DIR/logits.npy (fp32; the inputs and the model are the
+same from run to run, so two builds compare output for output).  ``--full``
+adds everything else the line can carry: ``sustained``, a ``roofline`` object
+for the dominant kernel (HIP-event per-kernel timing over a second timed pass,
+rocprofv3 counter passes, the in-kernel clock), at N > 1 the all-gather's own
+time, at N = 1 ``cpu_baseline`` (the reference's StaticPTQModel path — torch.ao
+quantize_dynamic — timed on the host cores), ``top1`` and ``configs_extra``.
 """
 from __future__ import annotations
 
@@ -133,6 +139,26 @@ def save_payload(path, payload):
 
 def load_payload(path):
     return _dec(torch.load(path, weights_only=True))
+
+
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(directory, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: write what the timed step returned, {name: tensor}, as
+    DIR/<name>.npy in fp32.  An output over its share of ``max_bytes`` is cut to
+    a fixed, seeded sample of its rows (the same rows in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    share = max_bytes // max(1, len(arrays))
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        if a.nbytes > share:
+            a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1, 1)
+            rows = max(1, share // (a.shape[1] * 4))
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(rows, a.shape[0]),
+                                                           replace=False))
+            a = np.ascontiguousarray(a[keep])
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 WARMUP_MIN_S = 0.1   # untimed forwards after the W warmup steps, at least this long
@@ -517,6 +543,7 @@ class StepLoop:
         self.pending = [None, None]
         self.nstep = 0
         self.last_slot = 0
+        self.last_logits = None   # what the latest step's forward returned
 
     def _tdev(self):
         return self.dev if dist.get_backend() == "nccl" else "cpu"
@@ -537,8 +564,14 @@ class StepLoop:
                 self.pending[slot].wait()
                 self.pending[slot] = None
         self.last_slot = slot
+        self.last_logits = logits
         self.nstep += 1
         return logits
+
+    def outputs(self):
+        """What a caller of the latest step receives, after drain() and sync():
+        the whole job's logits (at N > 1 every rank's, gathered in rank order)."""
+        return {"logits": self.gathered[self.last_slot] if self.world > 1 else self.last_logits}
 
     def drain(self):   # every outstanding all-gather has completed on the current stream
         for i in range(2):
@@ -665,6 +698,8 @@ def main_rehearse(args):
     loop = StepLoop(forward, world, "cpu")
     warm_run = ramp_warmup(loop.step, loop.drain, args.warmup, world, "cpu", 0.0, sync=loop.sync)
     elapsed, rank_ms = loop.timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop.outputs())
     result = {"metric": "harness rehearsal (CPU, gloo): not the int8 path", "value": world * B * args.steps / elapsed,
               "unit": "rows/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
               "warmup_steps_run": warm_run, "ms_per_step": elapsed / args.steps * 1e3,
@@ -673,7 +708,8 @@ def main_rehearse(args):
                                               "per_gpu_batch": B, "parallelism": f"dp{world}"}}
     if world > 1:
         result["rank_ms_per_step"] = rank_ms
-        result["allgather"] = loop.allgather_timing(forward(), 3)
+        if args.full:
+            result["allgather"] = loop.allgather_timing(forward(), 3)
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
@@ -692,6 +728,15 @@ def main():
                          "ResNet-50: each timed region pays ~0.15-0.2 ms of start-up after its "
                          "synchronize, 2-4 %% of a 50-step region of 0.07-0.14 ms steps)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits the last of them returned (at "
+                         "N > 1 the gathered logits of every rank) to DIR/logits.npy in fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the metric also measure and check everything else the line can "
+                         "carry: sustained, per-kernel HIP events and the roofline, the rocprofv3 "
+                         "counter and clock passes, the all-gather's own time, the CPU baselines "
+                         "and top-1, configs_extra (--no-cpu / --no-pmc / --no-extra drop parts "
+                         "of it).  A plain run times the K steps and prints the line")
     ap.add_argument("--warmup-min-ms", type=float, default=WARMUP_MIN_S * 1e3,
                     help="after the W warmup steps, keep running untimed forwards until this many ms "
                          "of them have run (0: exactly W); see ramp_warmup()")
@@ -707,7 +752,7 @@ def main():
                     help="replay the forward as one HIP graph (measured slower: config 2 3.04 vs "
                          "3.11 M img/s, headline 5.9 vs 6.3 M img/s, profiles/r03_diag_graph_ab.txt)")
     ap.add_argument("--pipeline", type=int, default=0,
-                    help="also time the forward with this many batches in flight on as many "
+                    help="with --full: also time the forward with this many batches in flight on as many "
                          "HIP streams (QuantizedConvNet.run_pipelined, each batch its own buffers "
                          "and the full forward at its own batch size): a serving-throughput "
                          "field beside the metric, never the metric itself")
@@ -772,6 +817,35 @@ def main():
     elapsed, rank_ms = loop.timed(args.steps)
     images = world * B * args.steps
     value = images / elapsed
+    if args.dump_outputs and rank == 0:   # the last timed step's logits
+        dump_outputs(args.dump_outputs, loop.outputs())
+
+    result = {
+        "metric": METRIC if mode == "static" else METRIC_QDQ, "value": value, "unit": "images/sec", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_run,
+        "warmup_note": (f"the W warmup steps, then untimed steps until >= {args.warmup_min_ms:.0f} ms of "
+                        "back-to-back forwards have run (ramp_warmup; --warmup-min-ms 0 runs exactly W), "
+                        "so the timed region starts at the throughput the chip holds under load"),
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int8", "data": "synthetic", "hip_graph": bool(use_graph),
+        "config": {"workload": ("full static-PTQ SimpleConvNet, all conv+linear int8 (u8 x s8 -> i32), "
+                                "NHWC, per-tensor weights" if mode == "static" else
+                                "per-layer QDQ SimpleConvNet (CustomQuantizationModel, BASELINE configs[1]): "
+                                "every conv and fc1 int8 with the dequantize/ReLU/pool/quantize hand-off "
+                                "fused, fp32 fc2") + (" [per-channel]" if args.per_channel else ""),
+                   "global_batch": world * B, "per_gpu_batch": B, "image": [3, 32, 32],
+                   "parallelism": f"dp{world}", "collective": "all_gather logits (RCCL)" if world > 1 else None},
+    }
+    if world > 1:
+        result["rank_ms_per_step"] = rank_ms
+        result["rank_ms_spread"] = max(rank_ms) - min(rank_ms)
+    if not args.full:   # a plain run: the metric and nothing beside it
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- region S: sustained throughput, >= 1 s of back-to-back steps (a
     # field beside the metric, never the metric: `value` is the K-step region)
@@ -873,31 +947,15 @@ def main():
     if pmc_err:
         roof["pmc_error"] = pmc_err
 
-    result = {
-        "metric": METRIC if mode == "static" else METRIC_QDQ, "value": value, "unit": "images/sec", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_run,
-        "warmup_note": (f"the W warmup steps, then untimed steps until >= {args.warmup_min_ms:.0f} ms of "
-                        "back-to-back forwards have run (ramp_warmup; --warmup-min-ms 0 runs exactly W), "
-                        "so the timed region starts at the throughput the chip holds under load"),
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int8", "data": "synthetic", "hip_graph": bool(use_graph),
+    result.update({
         "sustained": sustained,
-        "config": {"workload": ("full static-PTQ SimpleConvNet, all conv+linear int8 (u8 x s8 -> i32), "
-                                "NHWC, per-tensor weights" if mode == "static" else
-                                "per-layer QDQ SimpleConvNet (CustomQuantizationModel, BASELINE configs[1]): "
-                                "every conv and fc1 int8 with the dequantize/ReLU/pool/quantize hand-off "
-                                "fused, fp32 fc2") + (" [per-channel]" if args.per_channel else ""),
-                   "global_batch": world * B, "per_gpu_batch": B, "image": [3, 32, 32],
-                   "parallelism": f"dp{world}", "collective": "all_gather logits (RCCL)" if world > 1 else None},
         "roofline": roof,
         "kernels": {n: {kk: round(vv, 4) if isinstance(vv, float) else vv for kk, vv in kern[n].items()}
                     for n in names},
-    }
+    })
     if pipelined is not None:
         result["pipelined"] = pipelined
     if world > 1:
-        result["rank_ms_per_step"] = rank_ms
-        result["rank_ms_spread"] = max(rank_ms) - min(rank_ms)
         result["allgather"] = gather
     ph = kern.get("conv1_6", {}).get("phase_table")
     if ph:
@@ -946,7 +1004,7 @@ def extra_configs(args):
     default run carries them.  Extra keys beside the metric, never it."""
     out = {}
     for key, wl in (("configs[1]", "qdq"), ("configs[4]", "resnet50")):
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--no-cpu"]
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--full", "--no-cpu"]
         # the ResNet child's own two rocprofv3 counter passes would not fit its
         # time limit beside its run: its line keeps HIP-event times only
         if args.no_pmc or wl == "resnet50":
@@ -1045,7 +1103,9 @@ def main_resnet(args):
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     B = args.batch
-    fp = synthetic_resnet(0, device=dev, calib_images=32)
+    # the fp32 net's BN statistics pass runs on the host, like the calibration:
+    # on the GPU it differed from process to process, and with it the model
+    fp = synthetic_resnet(0, device="cpu", calib_images=32)
     calib = [torch.from_numpy(synthetic_images(32, 1 + i)) for i in range(2)]
     model = quantize_resnet(fp, calib, dev, per_channel=True)
     model.fuse_reduce = not args.separate_reduce
@@ -1066,6 +1126,7 @@ def main_resnet(args):
             logits = model.run(x, marks=marks)
         if world > 1:
             qd.gather_logits(logits, gathered)
+        return gathered if world > 1 else logits
 
     def barrier():
         if world > 1:
@@ -1075,8 +1136,9 @@ def main_resnet(args):
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -1085,6 +1147,26 @@ def main_resnet(args):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0 and out is not None:   # the last timed step's logits
+        dump_outputs(args.dump_outputs, {"logits": out})
+    result = {
+        "metric": METRIC_RESNET, "value": value, "unit": "images/sec", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_run,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int8",
+        "data": "synthetic",
+        "config": {"workload": "ResNet-50 (stem, 16 bottleneck blocks, avgpool, fc) static int8, "
+                               "per-channel weights, u8 NHWC activations",
+                   "global_batch": world * B, "per_gpu_batch": B, "image": [3, 224, 224],
+                   "parallelism": f"dp{world}", "streams": args.streams},
+    }
+    if not args.full:   # a plain run: the metric and nothing beside it
+        if rank == 0:
+            print(json.dumps(result))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # MACs per image of every conv launch, in forward order
     convs = model.conv_layers()
@@ -1147,21 +1229,12 @@ def main_resnet(args):
                 roof.update(resnet_traffic(B))
             except Exception as e:   # the fields stay null
                 roof["pmc_error"] = f"{type(e).__name__}: {e}"
-    result = {
-        "metric": METRIC_RESNET, "value": value, "unit": "images/sec", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "warmup_steps_run": warm_run,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int8",
-        "data": "synthetic",
-        "config": {"workload": "ResNet-50 (stem, 16 bottleneck blocks, avgpool, fc) static int8, "
-                               "per-channel weights, u8 NHWC activations",
-                   "global_batch": world * B, "per_gpu_batch": B, "image": [3, 224, 224],
-                   "parallelism": f"dp{world}", "streams": args.streams},
+    result.update({
         "roofline": roof,
         "launch_ms": {k: round(float(np.sum(v) / n_rep), 4) for k, v in per_name.items()},
         "conv_gmac_per_image": sum(mac_img) / 1e9,
         "conv_algorithmic_bytes_per_image": conv_bytes,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu:
         cb, q_cpu = resnet_cpu_baseline(fp, args.cpu_seconds)
         result["cpu_baseline"] = cb["static_int8"]

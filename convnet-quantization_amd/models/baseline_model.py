@@ -99,22 +99,57 @@ def trained_synthetic_model(seed=0, steps=400, batch=256, device="cuda", lr=2e-3
     (qconvnet.data.synthetic_task) — a bench/test fixture standing in for the
     reference's trained CIFAR-10 checkpoint (model_trainer.py), which is not
     available offline.  A trained net has real decision margins, so top-1
-    deltas between quantization schemes mean what they mean on CIFAR-10."""
+    deltas between quantization schemes mean what they mean on CIFAR-10.
+
+    The same seed gives the same weights, bit for bit, in every process (the
+    bench's --dump-outputs compares builds output for output).  MIOpen's convs
+    did not: the same training differed from process to process from the first
+    step on.  So the training runs with MIOpen off and torch's deterministic
+    algorithms on (both restored afterwards), and each 3x3 conv as im2col
+    (F.unfold) + one batched matmul, since torch's own conv without MIOpen
+    loops over the images (400 steps: ~40 s against ~8 s)."""
+    import os
+
     from qconvnet import data
-    torch.manual_seed(seed)
-    dev = torch.device(device)
-    model = SimpleConvNet().to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=lr)
-    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, steps)
-    model.train()
-    for it in range(steps):
-        x, y = data.synthetic_task(batch, 10_000 + seed * 100_003 + it)
-        x, y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
-        loss = torch.nn.functional.cross_entropy(model(x), y)
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        opt.step()
-        sched.step()
+
+    def conv_gemm(conv, x):
+        n, _, hh, ww = x.shape
+        cols = F.unfold(x, 3, padding=1)                        # [N, Cin*9, H*W]
+        out = torch.matmul(conv.weight.flatten(1), cols)        # [N, Cout, H*W]
+        return out.view(n, -1, hh, ww) + conv.bias.view(1, -1, 1, 1)
+
+    saved = (torch.backends.cudnn.enabled, torch.are_deterministic_algorithms_enabled(),
+             torch.is_deterministic_algorithms_warn_only_enabled(),
+             os.environ.get("CUBLAS_WORKSPACE_CONFIG"))
+    # torch asks for this setting before a deterministic matmul
+    os.environ.setdefault("CUBLAS_WORKSPACE_CONFIG", ":4096:8")
+    torch.backends.cudnn.enabled = False
+    torch.use_deterministic_algorithms(True)
+    try:
+        torch.manual_seed(seed)
+        dev = torch.device(device)
+        model = SimpleConvNet().to(dev)
+        convs = [m for m in model.modules() if isinstance(m, nn.Conv2d)]
+        for m in convs:
+            m.forward = lambda x, c=m: conv_gemm(c, x)
+        opt = torch.optim.Adam(model.parameters(), lr=lr)
+        sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, steps)
+        model.train()
+        for it in range(steps):
+            x, y = data.synthetic_task(batch, 10_000 + seed * 100_003 + it)
+            x, y = torch.from_numpy(x).to(dev), torch.from_numpy(y).to(dev)
+            loss = torch.nn.functional.cross_entropy(model(x), y)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+            sched.step()
+        for m in convs:
+            del m.forward   # the instance's override; the class's forward is back
+    finally:
+        torch.backends.cudnn.enabled = saved[0]
+        torch.use_deterministic_algorithms(saved[1], warn_only=saved[2])
+        if saved[3] is None:
+            os.environ.pop("CUBLAS_WORKSPACE_CONFIG", None)
     return model.eval().cpu()
 
 

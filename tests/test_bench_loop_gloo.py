@@ -98,11 +98,13 @@ def test_bench_step_loop_two_ranks_matches_single_process():
     assert len(res[0]["slots"]) == len(res[1]["slots"])
 
 
-def test_bench_gpus_2_without_torchrun_starts_two_ranks():
+def test_bench_gpus_2_without_torchrun_starts_two_ranks(tmp_path):
     """`python bench.py --gpus 2` with no torchrun env starts torch.distributed.run
     with two ranks as a child (never one rank labelled two): the line reports
     n_gpus 2 and both ranks' step times.  The rehearsal mode runs the harness
-    on CPU over gloo with a stand-in forward."""
+    on CPU over gloo with a stand-in forward.
+    The all-gather's own time is a --full field; --dump-outputs writes the
+    gathered logits of the last timed step, rank order == row order."""
     import json
     import subprocess
     import sys
@@ -112,7 +114,8 @@ def test_bench_gpus_2_without_torchrun_starts_two_ranks():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["CUDA_VISIBLE_DEVICES"] = ""
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse",
-                        "--steps", "3", "--warmup", "1", "--batch", "4"], cwd=root, env=env,
+                        "--steps", "3", "--warmup", "1", "--batch", "4", "--full",
+                        "--dump-outputs", str(tmp_path)], cwd=root, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -122,3 +125,12 @@ def test_bench_gpus_2_without_torchrun_starts_two_ranks():
     assert len(d["rank_ms_per_step"]) == 2 and all(v > 0 for v in d["rank_ms_per_step"])
     assert d["config"]["global_batch"] == 8
     assert d["allgather"]["bytes_per_rank"] == 4 * 10 * 4
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    # the stand-in forward of main_rehearse, rank by rank
+    w = torch.rand((3 * 32 * 32, 10), generator=torch.Generator().manual_seed(0))
+    want = torch.cat([torch.rand((4, 3 * 32 * 32), generator=torch.Generator().manual_seed(100 + r)) @ w
+                      for r in range(2)]).numpy()
+    got = np.load(os.path.join(str(tmp_path), "logits.npy"))
+    assert got.dtype == np.float32 and got.shape == (8, 10)
+    # fp32 sums over K = 3072 in whatever order the ranks' thread count gives
+    assert np.allclose(got, want, rtol=1e-5, atol=0)

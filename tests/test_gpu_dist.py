@@ -106,7 +106,7 @@ def _bench_worker(rank, port, q):
         import sys
         import bench
         sys.argv = ["bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "256",
-                    "--no-cpu", "--no-pmc"]
+                    "--full", "--no-cpu", "--no-pmc"]
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             bench.main()

@@ -10,7 +10,7 @@ cd $R
 ( while sleep 50; do echo "alive $(date +%T)"; done ) &
 HB=$!
 trap "kill $HB" EXIT
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err
 echo bench-ok
 cat $O/bench.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline'].get('frac'), list(d.get('configs_extra',{}).keys()))"
 echo done > $O/DONE

@@ -7,4 +7,4 @@ set -e
 O=$GRAFT_REPO_ROOT/gpurun_out/${1:-diag}
 mkdir -p $O
 bash tools/gpu_trace_gaps.sh ${1:-diag}
-timeout -k 10 300 python bench.py --workload qdq --no-pmc > $O/bench_qdq.json 2> $O/bench_qdq.err
+timeout -k 10 300 python bench.py --full --workload qdq --no-pmc > $O/bench_qdq.json 2> $O/bench_qdq.err

@@ -9,7 +9,7 @@ L=convnet-quantization_amd/qconvnet
 for r in 1 2; do
   for v in prod fcu8 fcu2; do
     if [ $v = prod ]; then lib=$L/libqconvnet.so; else lib=$L/libqconvnet_$v.so; fi
-    QCN_LIB=$lib timeout -k 10 200 python bench.py --no-cpu --no-pmc --steps 400 > $O/$v.$r.json 2> $O/$v.$r.err
+    QCN_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu --no-pmc --steps 400 > $O/$v.$r.json 2> $O/$v.$r.err
     python3 -c "
 import json,sys
 d=json.loads([l for l in open('$O/$v.$r.json') if l.startswith('{')][0])

@@ -10,8 +10,8 @@ import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']
 print('$1 %.0f img/s %.4f ms ' % (d['value'], d['ms_per_step']) + ' '.join('%s=%.1f' % (n, v['ms']*1e3) for n, v in k.items()))"
 }
 for A in --graph --no-graph --graph; do
-  timeout -k 10 300 python bench.py --workload qdq --no-cpu --no-pmc $A 2>/dev/null | line "qdq $A"
+  timeout -k 10 300 python bench.py --full --workload qdq --no-cpu --no-pmc $A 2>/dev/null | line "qdq $A"
 done
 for A in --graph --no-graph --graph --no-graph; do
-  timeout -k 10 300 python bench.py --no-cpu --no-pmc $A 2>/dev/null | line "convnet $A"
+  timeout -k 10 300 python bench.py --full --no-cpu --no-pmc $A 2>/dev/null | line "convnet $A"
 done

@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -x -v -m gpu -k "resnet or stream or
 for r in 1 2; do
   for v in prod jaff0; do
     if [ $v = prod ]; then lib=$L/libqconvnet.so; else lib=$L/libqconvnet_$v.so; fi
-    QCN_LIB=$lib timeout -k 10 300 python bench.py --workload resnet50 --no-cpu --no-pmc > $O/$v.$r.json 2> $O/$v.$r.err
+    QCN_LIB=$lib timeout -k 10 300 python bench.py --full --workload resnet50 --no-cpu --no-pmc > $O/$v.$r.json 2> $O/$v.$r.err
     python3 -c "
 import json
 d=json.loads([l for l in open('$O/$v.$r.json') if l.startswith('{')][0])

@@ -11,7 +11,7 @@ tail -2 $O/tests.log
 for r in 1 2; do
   for v in rn0 prod; do
     if [ $v = prod ]; then lib=$L/libqconvnet.so; else lib=$L/libqconvnet_$v.so; fi
-    QCN_LIB=$lib timeout -k 10 300 python bench.py --workload resnet50 --no-cpu --no-pmc > $O/bench_$v$r.json 2> $O/bench_$v$r.err
+    QCN_LIB=$lib timeout -k 10 300 python bench.py --full --workload resnet50 --no-cpu --no-pmc > $O/bench_$v$r.json 2> $O/bench_$v$r.err
     python -c "import json; d=json.loads(open('$O/bench_$v$r.json').read().strip().splitlines()[-1]); print('$v round $r', round(d['value']), d['ms_per_step'])" | tee -a $O/ab.txt
   done
 done

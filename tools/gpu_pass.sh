@@ -10,4 +10,4 @@ else
   timeout -k 10 900 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1
 fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout -k 10 700 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 700 python bench.py --full > $O/bench.json 2> $O/bench.err

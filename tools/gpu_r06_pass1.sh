@@ -10,7 +10,7 @@ for r in 1 2; do
   for v in prod r05; do
     if [ $v = prod ]; then lib=$L/libqconvnet.so; else lib=$L/libqconvnet_$v.so; fi
     echo "## $v round $r" >> $O/r06_p1_ab.txt
-    QCN_LIB=$lib timeout -k 10 200 python bench.py --no-cpu --no-pmc --no-extra --steps 400 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(round(d['value']/1e6,4), 'M img/s', round(d['ms_per_step']*1e3,2), 'us/step', {k: v['ms']*1e3 for k, v in d['kernels'].items()})" >> $O/r06_p1_ab.txt || exit 1
+    QCN_LIB=$lib timeout -k 10 200 python bench.py --full --no-cpu --no-pmc --no-extra --steps 400 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(round(d['value']/1e6,4), 'M img/s', round(d['ms_per_step']*1e3,2), 'us/step', {k: v['ms']*1e3 for k, v in d['kernels'].items()})" >> $O/r06_p1_ab.txt || exit 1
   done
 done
 if [ -f tools/clock/libqconvnet_clock.so ]; then

@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_resnet.py -x -v -m gpu --ti
 echo tests-ok
 for i in 1 2 3; do
   for F in "" "--separate-reduce"; do
-    timeout -k 10 300 python bench.py --workload resnet50 --no-cpu --no-pmc $F 2>/dev/null | python -c "
+    timeout -k 10 300 python bench.py --full --workload resnet50 --no-cpu --no-pmc $F 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('%-20s %9.0f img/s  %.3f ms/step' % ('[$F]', d['value'], d['ms_per_step']))" | tee -a $O/ab.txt
   done
 done

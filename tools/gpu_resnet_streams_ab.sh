@@ -4,7 +4,7 @@ set -e
 O=gpurun_out/${1:-rs}
 mkdir -p $O
 for s in 2 3 4 2 3; do
-  timeout -k 10 300 python bench.py --workload resnet50 --no-cpu --no-pmc --streams $s > $O/s$s.json 2> $O/s$s.err
+  timeout -k 10 300 python bench.py --full --workload resnet50 --no-cpu --no-pmc --streams $s > $O/s$s.json 2> $O/s$s.err
   python3 -c "
 import json
 d=json.loads([l for l in open('$O/s$s.json') if l.startswith('{')][0])

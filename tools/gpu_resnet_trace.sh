@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/t -o run -- python3 $R/bench.py --workload resnet50 --no-cpu --no-pmc --steps 20 --warmup 5 > $O/trace.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $O/t -o run -- python3 $R/bench.py --full --workload resnet50 --no-cpu --no-pmc --steps 20 --warmup 5 > $O/trace.log 2>&1
 cd $R
 cp $O/t/run_kernel_stats.csv $O/kernel_stats.csv
 find $O -name '*_kernel_trace.csv' -delete

@@ -15,7 +15,7 @@ ARGS=()
 for L in "$@"; do ARGS+=("QCN_LIB=$R/$L"); done
 for i in 1 2 3; do
   for E in "${ARGS[@]}"; do
-    env $E timeout -k 10 300 python bench.py --steps 100 --warmup 20 --no-cpu --no-pmc --no-extra 2>/dev/null | python -c "
+    env $E timeout -k 10 300 python bench.py --full --steps 100 --warmup 20 --no-cpu --no-pmc --no-extra 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['kernels']
 print('%-40s %9.0f img/s  ' % ('$E'[-40:], d['value']) + ' '.join('%s=%.1f' % (n, v['ms']*1e3) for n, v in k.items()))" | tee -a $O/ab.txt
   done
