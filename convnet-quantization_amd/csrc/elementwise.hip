@@ -243,7 +243,7 @@ __global__ void channel_affine_kernel(const float* __restrict__ x, int rows, int
 
 extern "C" {
 
-int qcn_version(void) { return 100; }
+int qcn_version(void) { return 101; }
 
 int qcn_quantize_f32_u8(const float* x, uint8_t* q, int n, int c, int h, int w, int nhwc_out,
                         float scale, int zero_point, void* stream) {

@@ -51,11 +51,13 @@ class CustomQuantizationModel(nn.Module):
         self.model.load_state_dict(load_checkpoint_state(state_dict))
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
-                 max_batches=None):
+                 max_batches=None, observer="minmax"):
+        """observer: "minmax" (default) or "histogram" (torch.ao's default
+        HistogramObserver on every stub, reduce_range=False)."""
         self.model.eval()
         folded = fold_state_dict(self.model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)
-        ranges = calibrate(folded, batches, calibration_device)
+        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="qdq")
         spec = build_qspec(folded, ranges, "qdq", per_channel)
         self.quantized_model = QuantizedConvNet(spec, self.device)
         return self.quantized_model

@@ -39,9 +39,12 @@ class StaticPTQModel:
         self.fp32_model.load_state_dict(load_checkpoint_state(state_dict))
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
-                 max_batches=None):
+                 max_batches=None, observer="minmax"):
         """Calibrate (fp32, BN folded — the reference quantizes on the CPU, so
-        does the default here) and build the int8 GPU model."""
+        does the default here) and build the int8 GPU model.  observer:
+        "minmax" (default) or "histogram", torch.ao's default
+        HistogramObserver (get_default_qconfig('fbgemm') activations,
+        reduce_range=False)."""
         self.fp32_model.eval()
         if self.mode == "reference":
             from models.dynamic_ptq_model import DynamicQuantConvNet
@@ -50,7 +53,7 @@ class StaticPTQModel:
             return self.quantized_model
         folded = fold_state_dict(self.fp32_model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)
-        ranges = calibrate(folded, batches, calibration_device)
+        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="static")
         spec = build_qspec(folded, ranges, "static", per_channel)
         self.quantized_model = QuantizedConvNet(spec, self.device)
         return self.quantized_model

@@ -48,6 +48,7 @@ SIGNATURES = {
     "qcn_dequantize_u8_f32": (i32, [vp, vp, i64, f32, i32, vp]),
     "qcn_minmax_reset": (i32, [vp, vp]),
     "qcn_minmax_f32": (i32, [vp, i64, vp, vp]),
+    "qcn_histc_f32": (i32, [vp, i64, vp, i32, vp, vp]),
     "qcn_maxpool2x2_u8_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "qcn_argmax_f32": (i32, [vp, i32, i32, vp, vp]),
     "qcn_channel_affine_f32": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),

@@ -2,6 +2,8 @@
 memory + the current HIP stream).  Every op launches on
 ``torch.cuda.current_stream()`` and never synchronizes, so sequences of them
 can be captured in a HIP graph (torch.cuda.CUDAGraph is hipGraph on ROCm).
+The one exception is ``HistogramObserver.__call__`` (calibration only): it
+copies its counts to the host, one sync per call.
 """
 from __future__ import annotations
 
@@ -76,6 +78,71 @@ class MinMaxObserver:
     def values(self):
         v = self.state.cpu().numpy()
         return np.float32(v[0]), np.float32(v[1])
+
+
+def histc(x, minmax, bins=2048, out=None):
+    """ADDS torch.histc(x, bins, min=minmax[0], max=minmax[1]) into ``out``
+    (device int32 [bins] holding uint32 counts; a zeroed one is made when
+    None).  ``minmax``: device float[2], e.g. a MinMaxObserver's state.  ``x``
+    may start at any 4-byte boundary (a flat view of a contiguous tensor)."""
+    _need(x, torch.float32, "histc.x")
+    _need(minmax, torch.float32, "histc.minmax")
+    if minmax.numel() != 2:
+        raise ValueError("histc.minmax: expected 2 floats")
+    if out is None:
+        out = torch.zeros(bins, dtype=torch.int32, device=x.device)
+    _need(out, torch.int32, "histc.out")
+    if out.numel() != bins:
+        raise ValueError("histc.out: expected one count per bin")
+    check(lib().qcn_histc_f32(_ptr(x), x.numel(), _ptr(minmax), int(bins), _ptr(out), _stream()),
+          "histc")
+    return out
+
+
+class HistogramObserver:
+    """torch.ao's HistogramObserver(reduce_range=False) with the data on the
+    device: per call, qcn_minmax_f32 into the running device range, a zeroed
+    device uint32[bins], qcn_histc_f32 over that range, ONE device-to-host
+    copy of the counts and the range, and the host combine
+    (quant.HistogramState) into the fp32 ``histogram`` / ``min_val`` /
+    ``max_val``.  That copy is one host sync per call — accepted for
+    calibration, and the one place in this module that synchronizes; the
+    observer is therefore not graph-capturable.  Counts are exact integers
+    (torch counts in fp32: equal while every bin of a batch stays below 2^24).
+    Inputs holding +-inf or NaN are outside the contract (torch filters inf)."""
+
+    def __init__(self, device="cuda", bins=2048):
+        from .quant import HistogramState
+        self.bins = int(bins)
+        self.host = HistogramState(self.bins)
+        # counts and the running range share one buffer so one copy brings both
+        self._buf = torch.zeros(self.bins + 2, dtype=torch.int32, device=device)
+        self._hist = self._buf[:self.bins]
+        self.state = self._buf[self.bins:].view(torch.float32)
+        check(lib().qcn_minmax_reset(_ptr(self.state), _stream()), "minmax_reset")
+
+    histogram = property(lambda self: self.host.histogram)
+    min_val = property(lambda self: self.host.min_val)
+    max_val = property(lambda self: self.host.max_val)
+
+    def __call__(self, x):
+        _need(x, torch.float32, "histogram.x")
+        if x.numel() == 0:
+            return x
+        check(lib().qcn_minmax_f32(_ptr(x), x.numel(), _ptr(self.state), _stream()), "minmax")
+        self._hist.zero_()
+        check(lib().qcn_histc_f32(_ptr(x), x.numel(), _ptr(self.state), self.bins, _ptr(self._hist),
+                                  _stream()), "histc")
+        raw = self._buf.cpu().numpy()
+        rng = raw[self.bins:].view(np.float32)
+        counts = raw[:self.bins].view(np.uint32).astype(np.float32)
+        self.host.update(float(rng[0]), float(rng[1]), torch.from_numpy(counts))
+        return x
+
+    def values(self):
+        """The searched (new_min, new_max) as two np.float32;
+        quant.qparams_affine(*values()) equals torch's calculate_qparams()."""
+        return self.host.search()
 
 
 # --------------------------------------------------------------- A10 / A11

@@ -78,32 +78,97 @@ class _Range:
         return self.obs.values() if self.obs is not None else (self.lo, self.hi)
 
 
-def calibrate(folded, batches, device="cpu"):
+class _HistRange:
+    """torch.ao's HistogramObserver(reduce_range=False) on one activation
+    (observer.py:1289-1370): the HIP histogram kernel on GPU, torch.aminmax +
+    torch.histc on CPU, the same host combine and search behind both.
+    values() is the searched clipping range, not the raw min/max."""
+
+    def __init__(self, device):
+        self.dev = torch.device(device)
+        self.obs = ops.HistogramObserver(self.dev) if self.dev.type == "cuda" else \
+            Q.HistogramState()
+
+    def __call__(self, x):
+        if x.numel() == 0:
+            return
+        if self.dev.type == "cuda":
+            self.obs(x.contiguous())
+        else:
+            self.obs.observe_host(x)
+
+    def values(self):
+        return self.obs.values() if self.dev.type == "cuda" else self.obs.search()
+
+
+_OBSERVERS = {"minmax": _Range, "histogram": _HistRange}
+
+
+def _observed_names(mode):
+    """The observers build_qspec(mode) reads; all of them for mode None."""
+    convs = [f"conv{i}" for i in range(1, 7)]
+    if mode is None:
+        return ["x"] + [f"{c}_{s}" for c in convs for s in ("in", "out")] + \
+            ["fc1_in", "fc1_out", "fc2_out"]
+    if mode == "static":
+        return ["x"] + [f"{c}_out" for c in convs] + ["fc1_out", "fc2_out"]
+    if mode == "qdq":
+        return [f"{c}_{s}" for c in convs for s in ("in", "out")] + ["fc1_in", "fc1_out"]
+    raise ValueError(f"unknown mode {mode!r}")
+
+
+def calibrate(folded, batches, device="cpu", observer="minmax", mode=None):
     """Run the BN-folded fp32 net over calibration batches and record the
-    ranges every observer of the static and the QDQ configuration needs."""
+    range of every observer ``mode`` needs ("static", "qdq"; None: those of
+    both) as {name: (lo, hi)} for build_qspec.
+
+    observer="minmax" (default): the running min/max.  observer="histogram":
+    torch.ao's default HistogramObserver (2048 bins, reduce_range=False); the
+    range is its searched clipping range, so Q.qparams_affine of it is
+    calculate_qparams().  A histogram cannot be clamped after the fact the way
+    build_qspec's _relu_range clamps a min/max, so with mode="static" the
+    conv{i}_out / fc1_out histogram observers see the POST-ReLU tensor, as the
+    output observers of torch.ao's fused ConvReLU2d / LinearReLU do (and
+    _relu_range is then a no-op); with mode="qdq" they see the pre-ReLU
+    output, as the per-layer stubs do.  The mode is therefore required."""
+    if observer not in _OBSERVERS:
+        raise ValueError(f"unknown observer {observer!r} (expected one of {sorted(_OBSERVERS)})")
+    if observer == "histogram" and mode is None:
+        raise ValueError("observer='histogram' needs mode='static' or 'qdq'")
+    names = _observed_names(mode)
+    post_relu = observer == "histogram" and mode == "static"
     dev = torch.device(device)
     t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in folded.items()}
-    names = ["x"] + [f"conv{i}_{s}" for i in range(1, 7) for s in ("in", "out")] + \
-        ["fc1_in", "fc1_out", "fc2_out"]
-    rng = {n: _Range(dev) for n in names}
+    rng = {n: _OBSERVERS[observer](dev) for n in names}
+
+    def see(name, x):
+        if name in rng:
+            rng[name](x)
+
     with torch.no_grad():
         for xb in batches:
             x = xb.to(dev, torch.float32)
-            rng["x"](x)
+            see("x", x)
             for i, (_, _, pool) in enumerate(CONV_TABLE, start=1):
-                rng[f"conv{i}_in"](x)
+                see(f"conv{i}_in", x)
                 x = F.conv2d(x, t[f"conv{i}.w"], t[f"conv{i}.b"], padding=1)
-                rng[f"conv{i}_out"](x)
+                if not post_relu:
+                    see(f"conv{i}_out", x)
                 x = F.relu(x)
+                if post_relu:
+                    see(f"conv{i}_out", x)
                 if pool:
                     x = F.max_pool2d(x, 2, 2)
             x = x.reshape(x.shape[0], -1)
-            rng["fc1_in"](x)
+            see("fc1_in", x)
             x = F.linear(x, t["fc1.w"], t["fc1.b"])
-            rng["fc1_out"](x)
+            if not post_relu:
+                see("fc1_out", x)
             x = F.relu(x)
+            if post_relu:
+                see("fc1_out", x)
             x = F.linear(x, t["fc2.w"], t["fc2.b"])
-            rng["fc2_out"](x)
+            see("fc2_out", x)
     return {n: r.values() for n, r in rng.items()}
 
 

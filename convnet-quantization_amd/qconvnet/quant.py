@@ -13,11 +13,17 @@ vectors in tests/golden/ pin it; tests/test_host_quant.py checks it):
   /root/reference/models/dynamic_ptq_model.py:289-299;
 * quantize_weight — the weight quantization done by from_float;
 * epilogue_constants — FBGEMM ReQuantizeOutput's fp32 constants
-  (torch/include/fbgemm/OutputProcessing-inl.h:76-127, vector form).
+  (torch/include/fbgemm/OutputProcessing-inl.h:76-127, vector form);
+* hist_combine / hist_upscale / hist_param_search / hist_quantization_error and
+  HistogramState — HistogramObserver's host half (torch/ao/quantization/
+  observer.py:1076-1370).  These are built from torch CPU ops in torch's own
+  order: its fp32 sum, cumsum, linspace, bucketize and bincount fix the
+  rounding, which a numpy re-derivation would not reproduce.
 """
 from __future__ import annotations
 
 import numpy as np
+import torch
 
 F32 = np.float32
 EPS = F32(np.finfo(np.float32).eps)
@@ -132,3 +138,165 @@ def nhwc_flatten_perm(c=256, h=4, w=4):
     pooled tensor while keeping baseline_model.py:78's NCHW flatten semantics."""
     idx = np.arange(c * h * w).reshape(c, h, w)
     return np.ascontiguousarray(np.transpose(idx, (1, 2, 0))).reshape(-1)
+
+
+# ------------------------------------------------------ HistogramObserver (host)
+HIST_BINS = 2048        # HistogramObserver's default
+HIST_UPSAMPLE = 16      # observer.py:1056-1058
+HIST_DST_NBINS = 256    # 2 ** bits of quint8, reduce_range=False (observer.py:1055)
+
+
+def hist_upscale(histogram, orig_min, orig_max, update_min, update_max, bins=HIST_BINS):
+    """_upscale_histogram (observer.py:1194-1233): the old histogram, split
+    16-fold, re-binned by its sub-bin midpoints into the new range's bins."""
+    histogram = histogram.repeat_interleave(HIST_UPSAMPLE) / HIST_UPSAMPLE
+    bin_size = (orig_max - orig_min) / (bins * HIST_UPSAMPLE)
+    mid_points = torch.linspace(orig_min, orig_max, bins * HIST_UPSAMPLE + 1)[:-1] + 0.5 * bin_size
+    boundaries = torch.linspace(update_min, update_max, bins + 1)
+    bucket = torch.bucketize(mid_points, boundaries, right=True) - 1
+    bucket[bucket >= bins] = bins - 1
+    bucket[bucket < 0] = 0
+    return torch.bincount(bucket, weights=histogram, minlength=bins)
+
+
+def hist_combine(orig_hist, orig_min, orig_max, update_hist, update_min, update_max,
+                 bins=HIST_BINS):
+    """_combine_histograms (observer.py:1235-1274).  update_hist is already
+    binned over [update_min, update_max], which contains [orig_min, orig_max]."""
+    if update_min == orig_min and update_max == orig_max:
+        return orig_hist + update_hist
+    if orig_min == orig_max:   # the old histogram holds one value
+        bin_value = torch.sum(orig_hist)
+        moved = torch.histc(orig_min, bins=bins, min=update_min, max=update_max) * bin_value
+        return moved + update_hist
+    if update_min > orig_min or update_max < orig_max:
+        raise AssertionError("the updated range must contain the old one")
+    return update_hist + hist_upscale(orig_hist, orig_min, orig_max, update_min, update_max, bins)
+
+
+def _hist_norm(delta_begin, delta_end, density):
+    """_get_norm (observer.py:1060-1074): density * (end^3 - begin^3) / 3."""
+    norm = (delta_end * delta_end * delta_end - delta_begin * delta_begin * delta_begin) / 3
+    return density * norm
+
+
+def hist_quantization_error(histogram, min_val, max_val, next_start_bin, next_end_bin,
+                            bins=HIST_BINS, dst_nbins=HIST_DST_NBINS):
+    """_compute_quantization_error (observer.py:1076-1128).  bin_width comes
+    from .item() here, so it is a Python double (an fp32 tensor in the search
+    below); torch does the same and the rounding depends on it."""
+    bin_width = (max_val.item() - min_val.item()) / bins
+    dst_bin_width = bin_width * (next_end_bin - next_start_bin + 1) / dst_nbins
+    if dst_bin_width == 0.0:
+        return 0.0
+    src_bin = torch.arange(bins)
+    src_bin_begin = (src_bin - next_start_bin) * bin_width
+    src_bin_end = src_bin_begin + bin_width
+    dst_bin_of_begin = torch.clamp(torch.div(src_bin_begin, dst_bin_width, rounding_mode="floor"),
+                                   0, dst_nbins - 1)
+    dst_bin_of_begin_center = (dst_bin_of_begin + 0.5) * dst_bin_width
+    dst_bin_of_end = torch.clamp(torch.div(src_bin_end, dst_bin_width, rounding_mode="floor"),
+                                 0, dst_nbins - 1)
+    density = histogram / bin_width
+    norm = torch.zeros(bins)
+    delta_begin = src_bin_begin - dst_bin_of_begin_center
+    delta_end = dst_bin_width / 2
+    norm += _hist_norm(delta_begin, torch.ones(bins) * delta_end, density)
+    norm += (dst_bin_of_end - dst_bin_of_begin - 1) * _hist_norm(
+        torch.tensor(-dst_bin_width / 2), torch.tensor(dst_bin_width / 2), density)
+    dst_bin_of_end_center = dst_bin_of_end * dst_bin_width + dst_bin_width / 2
+    delta_begin = -dst_bin_width / 2
+    delta_end = src_bin_end - dst_bin_of_end_center
+    norm += _hist_norm(torch.tensor(delta_begin), delta_end, density)
+    return norm.sum().item()
+
+
+def hist_param_search(histogram, min_val, max_val, bins=HIST_BINS, dst_nbins=HIST_DST_NBINS):
+    """_non_linear_param_search (observer.py:1130-1192): shrink the range from
+    whichever end frees more bins per 1e-5 quantile step while the L2
+    quantization error does not grow.  Returns (new_min, new_max) fp32 tensors."""
+    bin_width = (max_val - min_val) / bins
+    total = torch.sum(histogram).item()
+    c_sum = torch.cumsum(histogram, dim=0)
+    stepsize = 1e-5
+    alpha, beta = 0.0, 1.0
+    start_bin, end_bin = 0, bins - 1
+    norm_min = float("inf")
+    while alpha < beta:
+        next_alpha = alpha + stepsize
+        next_beta = beta - stepsize
+        l, r = start_bin, end_bin
+        while l < end_bin and c_sum[l] < next_alpha * total:
+            l = l + 1
+        while r > start_bin and c_sum[r] > next_beta * total:
+            r = r - 1
+        next_start_bin, next_end_bin = start_bin, end_bin
+        if (l - start_bin) > (end_bin - r):
+            next_start_bin = l
+            alpha = next_alpha
+        else:
+            next_end_bin = r
+            beta = next_beta
+        if next_start_bin == start_bin and next_end_bin == end_bin:
+            continue
+        norm = hist_quantization_error(histogram, min_val, max_val, next_start_bin, next_end_bin,
+                                       bins, dst_nbins)
+        if norm > norm_min:
+            break
+        norm_min = norm
+        start_bin, end_bin = next_start_bin, next_end_bin
+    new_min = min_val + bin_width * start_bin
+    new_max = min_val + bin_width * (end_bin + 1)
+    return new_min, new_max
+
+
+class HistogramState:
+    """The running state of one HistogramObserver(reduce_range=False) on the
+    host: fp32 ``histogram`` [bins], ``min_val``, ``max_val`` (0-dim fp32 CPU
+    tensors), updated as HistogramObserver.forward does (observer.py:1289-1346)
+    from a batch's histogram over the NEW running range.  Whoever owns the
+    data (the HIP kernels, or torch.histc on the host) supplies that histogram;
+    the running range is min(old, batch min) / max(old, batch max).  Inputs
+    holding +-inf or NaN are outside the contract: torch filters inf before
+    observing, this does not."""
+
+    def __init__(self, bins=HIST_BINS):
+        self.bins = int(bins)
+        self.histogram = torch.zeros(self.bins)
+        self.min_val = torch.tensor(float("inf"))
+        self.max_val = torch.tensor(float("-inf"))
+
+    def initialized(self):
+        return not (self.min_val == float("inf") or self.max_val == float("-inf"))
+
+    def update(self, new_min, new_max, update_hist):
+        """new_min / new_max: the running range after this batch; update_hist:
+        this batch's counts over it (fp32, or integers below 2^24)."""
+        new_min = torch.as_tensor(new_min, dtype=torch.float32).reshape(())
+        new_max = torch.as_tensor(new_max, dtype=torch.float32).reshape(())
+        update_hist = torch.as_tensor(update_hist).to(torch.float32)
+        if not self.initialized():                      # reset_histogram (:1276-1287)
+            self.histogram = update_hist.clone()
+        elif new_min == self.min_val and new_max == self.max_val:
+            self.histogram = self.histogram + update_hist
+        else:
+            self.histogram = hist_combine(self.histogram, self.min_val, self.max_val, update_hist,
+                                          new_min, new_max, self.bins)
+        self.min_val, self.max_val = new_min.clone(), new_max.clone()
+
+    def observe_host(self, x):
+        """HistogramObserver.forward on a host tensor (aminmax + torch.histc)."""
+        if x.numel() == 0:
+            return
+        x = x.detach().to(torch.float32)
+        x_min, x_max = torch.aminmax(x)
+        new_min, new_max = torch.min(self.min_val, x_min), torch.max(self.max_val, x_max)
+        self.update(new_min, new_max, torch.histc(x, self.bins, min=new_min, max=new_max))
+
+    def search(self):
+        """(new_min, new_max) of calculate_qparams' search as two np.float32;
+        qparams_affine(*search()) is calculate_qparams() (:1348-1370)."""
+        if not self.initialized():
+            raise ValueError("the observer has seen no data")
+        lo, hi = hist_param_search(self.histogram, self.min_val, self.max_val, self.bins)
+        return F32(lo.item()), F32(hi.item())

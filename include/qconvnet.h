@@ -80,6 +80,25 @@ int qcn_dequantize_u8_f32(const uint8_t* q, float* x, long long count, float sca
 int qcn_minmax_reset(float* minmax, void* stream);
 int qcn_minmax_f32(const float* x, long long count, float* minmax, void* stream);
 
+/* HistogramObserver.forward's histogram (torch/ao/quantization/observer.py:
+ * 1289-1346; torch.ao's default activation observer, imported by the reference
+ * at models/custom_quantization_model.py:5): ADDS the torch.histc(x, bins,
+ * min, max) counts of x into hist[bins]; the caller zeroes hist.  minmax
+ * points to 2 DEVICE floats, the running [min, max] qcn_minmax_f32 has just
+ * updated, so no host round trip sits between the two launches.
+ *   bin = min(int(((v - lo) / (hi - lo)) * bins), bins - 1)  for lo <= v <= hi,
+ * every operation IEEE fp32 with a correctly rounded division; elements
+ * outside the range (and NaN) are skipped; lo == hi counts over [lo - 1,
+ * hi + 1]; the reset state [+inf, -inf] counts nothing.
+ * Counts are exact integers.  torch.histc accumulates them in fp32 per thread,
+ * so a torch bin above 2^24 saturates and depends on the thread count; the
+ * two are equal while every bin stays below 2^24.  Inputs holding +-inf are
+ * outside the contract (torch's observer filters them first; this does not).
+ * bins: a power of two, 16 <= bins <= 4096 (else QCN_ERR_UNSUPPORTED);
+ * 0 <= count < 2^32 (count == 0: no launch); x needs only 4-byte alignment. */
+int qcn_histc_f32(const float* x, long long count, const float* minmax, int bins,
+                  uint32_t* hist, void* stream);
+
 /* A10 — nn.MaxPool2d(2, 2) on u8 NHWC (baseline_model.py:17,25,33). */
 int qcn_maxpool2x2_u8_nhwc(const uint8_t* x, int n, int h, int w, int c, uint8_t* y,
                            void* stream);
