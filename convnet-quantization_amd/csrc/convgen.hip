@@ -150,13 +150,15 @@ __global__ __launch_bounds__(256) void conv_gen_kernel(const uint8_t* __restrict
 
 // out = quantize(relu?(dequantize(a) + dequantize(b))) with aten op order:
 // fp32(s) * (q - z) per operand, an IEEE fp32 add, max(., 0), then
-// quantize_per_tensor (zp added after rint).  16 elements per thread.
+// quantize_per_tensor (zp added after rint).  16 elements per thread: one
+// 16-byte access per operand when vec (every pointer 16-byte aligned), the
+// element loop otherwise and for the last, partial group.
 __global__ void add_relu_u8_kernel(const uint8_t* __restrict__ a, float sa, int za,
                                    const uint8_t* __restrict__ b, float sb, int zb, long count,
-                                   float inv_o, int zo, int relu, uint8_t* __restrict__ y) {
+                                   float inv_o, int zo, int relu, int vec, uint8_t* __restrict__ y) {
   const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 16;
   if (i0 >= count) return;
-  if (i0 + 16 <= count) {
+  if (vec && i0 + 16 <= count) {
     const uint4 va = *reinterpret_cast<const uint4*>(a + i0);
     const uint4 vb = *reinterpret_cast<const uint4*>(b + i0);
     const uint32_t wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
@@ -179,7 +181,8 @@ __global__ void add_relu_u8_kernel(const uint8_t* __restrict__ a, float sa, int 
     }
     *reinterpret_cast<uint4*>(y + i0) = make_uint4(wo[0], wo[1], wo[2], wo[3]);
   } else {
-    for (long i = i0; i < count; ++i) {
+    const long i1 = i0 + 16 < count ? i0 + 16 : count;
+    for (long i = i0; i < i1; ++i) {
       float s = sa * (float)((int)a[i] - za) + sb * (float)((int)b[i] - zb);
       if (relu) s = s > 0.0f ? s : 0.0f;
       const float t = fminf(fmaxf(s * inv_o, -1.0e9f), 1.0e9f);
@@ -227,6 +230,29 @@ __global__ void maxpool3x3s2_kernel(const uint8_t* __restrict__ x, int n, int h,
     }
   }
   *reinterpret_cast<uint4*>(y + p * c + cb * 16) = r;
+}
+
+// The same pool one byte per thread, for pointers that are not 16-byte aligned.
+__global__ void maxpool3x3s2_bytes_kernel(const uint8_t* __restrict__ x, int n, int h, int w, int c,
+                                          int oh, int ow, uint8_t* __restrict__ y) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)n * oh * ow * c) return;
+  const int ch = (int)(e % c);
+  const long p = e / c;
+  const int ox = (int)(p % ow), oy = (int)((p / ow) % oh);
+  const long img = p / ((long)ow * oh);
+  uint8_t r = 0;
+  for (int dy = -1; dy <= 1; ++dy) {
+    const int iy = 2 * oy + dy;
+    if (iy < 0 || iy >= h) continue;
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int ix = 2 * ox + dx;
+      if (ix < 0 || ix >= w) continue;
+      const uint8_t q = x[((img * h + iy) * w + ix) * c + ch];
+      r = q > r ? q : r;
+    }
+  }
+  y[e] = r;
 }
 
 // QuantStub + the row im2col of the 7x7/stride-2/pad-3 stem conv on 3 input
@@ -349,9 +375,15 @@ int qcn_maxpool3x3s2_u8_nhwc(const uint8_t* x, int nimg, int h, int w, int c, ui
   if (!x || !y || nimg <= 0 || h <= 0 || w <= 0 || c <= 0) return QCN_ERR_ARG;
   if (c % 16 != 0) return QCN_ERR_UNSUPPORTED;
   const int oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1;
-  const long total = (long)nimg * oh * ow * (c / 16);
-  hipLaunchKernelGGL(qcn::maxpool3x3s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, x, nimg, h, w, c, oh, ow, y);
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
+    const long total = (long)nimg * oh * ow * (c / 16);
+    hipLaunchKernelGGL(qcn::maxpool3x3s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, x, nimg, h, w, c, oh, ow, y);
+  } else {
+    const long total = (long)nimg * oh * ow * c;
+    hipLaunchKernelGGL(qcn::maxpool3x3s2_bytes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256),
+                       0, (hipStream_t)stream, x, nimg, h, w, c, oh, ow, y);
+  }
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 
@@ -383,9 +415,11 @@ int qcn_add_relu_u8(const uint8_t* a, float sa, int za, const uint8_t* b, float 
     return QCN_ERR_ARG;
   if (count == 0) return QCN_OK;
   const long th = (count + 15) / 16;
+  const int vec = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
+                    reinterpret_cast<uintptr_t>(y)) & 15) == 0;
   hipLaunchKernelGGL(qcn::add_relu_u8_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, a, sa, za, b, sb, zb, (long)count, 1.0f / s_out, z_out,
-                     relu, y);
+                     relu, vec, y);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 

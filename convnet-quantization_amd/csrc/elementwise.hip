@@ -232,8 +232,9 @@ __global__ void channel_affine_kernel(const float* __restrict__ x, int rows, int
     const float4 b = *reinterpret_cast<const float4*>(beta + c);
     float4 o = make_float4(__builtin_fmaf(v.x, a.x, b.x), __builtin_fmaf(v.y, a.y, b.y),
                            __builtin_fmaf(v.z, a.z, b.z), __builtin_fmaf(v.w, a.w, b.w));
-    if (relu) {
-      o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+    if (relu) {   // torch.relu: x where not x < 0, so -0.0 stays -0.0 (fmaxf would give +0.0)
+      o.x = o.x < 0.f ? 0.f : o.x; o.y = o.y < 0.f ? 0.f : o.y;
+      o.z = o.z < 0.f ? 0.f : o.z; o.w = o.w < 0.f ? 0.f : o.w;
     }
     reinterpret_cast<float4*>(y)[e] = o;
   }
@@ -243,7 +244,7 @@ __global__ void channel_affine_kernel(const float* __restrict__ x, int rows, int
 
 extern "C" {
 
-int qcn_version(void) { return 101; }
+int qcn_version(void) { return 102; }
 
 int qcn_quantize_f32_u8(const float* x, uint8_t* q, int n, int c, int h, int w, int nhwc_out,
                         float scale, int zero_point, void* stream) {

@@ -20,8 +20,8 @@
 // tests/golden/net_resnet_qdq.npz): dequantize fp32(q - z) * s; BN eval
 // y = fmaf(x, alpha, beta) with alpha / beta from ATen's eval constants
 // (host, qconvnet/quant.py bn_eval_affine); ReLU keeps -0.0 like
-// torch.relu; quantize zp + rint(x * fp32(1/s)) clamped; avg-pool a
-// sequential fp32 sum in row-major window order, then / (H*W).  All NHWC,
+// torch.relu; quantize zp + rint(x * fp32(1/s)) clamped; avg-pool an fp32
+// sum over the window in ATen's cascade order, then / (H*W).  All NHWC,
 // channel innermost, 4 channels per lane (C % 4 == 0).
 #include "common.hpp"
 #include "qconvnet_abi.hpp"
@@ -148,21 +148,43 @@ __global__ __launch_bounds__(256) void qdq_join_kernel(
   }
 }
 
-// [n][hw][c] fp32 -> [n][c]: one lane per (image, 4 channels), sequential sum
+QCN_DEV void add4(float4& a, const float4 v) { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
+
+// [n][hw][c] fp32 -> [n][c]: one lane per (image, 4 channels).  The window
+// is summed in the order of ATen's CPU sum kernel (adaptive_avg_pool2d to 1x1
+// is mean over H, W; multi_row_sum of SumKernel.cpp): 2^lp consecutive pixels
+// into level 0, each full level folded into the next one up (four levels),
+// the levels added lowest first at the end.  Up to 16 pixels that is the
+// plain sequential sum.  lp = max(4, ceil_log2(hw) / 4), from the host.
 __global__ __launch_bounds__(256) void avgpool_f32_kernel(const float* __restrict__ x, int n, int hw,
-                                                          int c, float* __restrict__ out) {
+                                                          int c, int lp, float* __restrict__ out) {
   const int c4 = c / 4;
+  const int step = 1 << lp, mask = step - 1;
   const long long total = (long long)n * c4;
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
     const int cg = (int)(i % c4), img = (int)(i / c4);
     const float4* p = reinterpret_cast<const float4*>(x + (long long)img * hw * c) + cg;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < hw; ++k) {
-      const float4 v = p[(long long)k * c4];
-      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 acc[4] = {zero, zero, zero, zero};
+    int k = 0;
+    while (k + step <= hw) {
+      for (int j = 0; j < step; ++j, ++k) add4(acc[0], p[(long long)k * c4]);
+      bool go = true;
+#pragma unroll
+      for (int j = 1; j < 4; ++j) {
+        if (go) {
+          add4(acc[j], acc[j - 1]);
+          acc[j - 1] = zero;
+          if ((k & (mask << (j * lp))) != 0) go = false;
+        }
+      }
     }
+    for (; k < hw; ++k) add4(acc[0], p[(long long)k * c4]);
+#pragma unroll
+    for (int j = 1; j < 4; ++j) add4(acc[0], acc[j]);
     const float d = (float)hw;
-    reinterpret_cast<float4*>(out)[i] = make_float4(acc.x / d, acc.y / d, acc.z / d, acc.w / d);
+    reinterpret_cast<float4*>(out)[i] =
+        make_float4(acc[0].x / d, acc[0].y / d, acc[0].z / d, acc[0].w / d);
   }
 }
 
@@ -225,8 +247,13 @@ int qcn_qdq_join_f32(const uint8_t* y3, float s3, int z3, const float* a3, const
 int qcn_avgpool_f32_nhwc(const float* x, int n, int h, int w, int c, float* out, void* stream) {
   if (!x || !out || n <= 0 || h <= 0 || w <= 0 || c <= 0 || c % 4) return QCN_ERR_ARG;
   if (!qcn::aligned(x, 16) || !qcn::aligned(out, 16)) return QCN_ERR_ARG;
+  if ((long long)h * w > 0x7fffffffLL) return QCN_ERR_UNSUPPORTED;
+  const int hw = h * w;
+  int log2c = 1;   // c10::utils::CeilLog2
+  while (hw > 2 && (1LL << log2c) < hw) ++log2c;
+  const int lp = log2c / 4 > 4 ? log2c / 4 : 4;
   hipLaunchKernelGGL(qcn::avgpool_f32_kernel, dim3(qcn::grid_of((long long)n * (c / 4))), dim3(256), 0,
-                     (hipStream_t)stream, x, n, h * w, c, out);
+                     (hipStream_t)stream, x, n, hw, c, lp, out);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 

@@ -76,7 +76,8 @@ int qcn_dequantize_u8_f32(const uint8_t* q, float* x, long long count, float sca
 
 /* A2 — MinMaxObserver.forward (torch/ao/quantization/observer.py:558-569):
  * running [min, max] of fp32 data, reduced on the device.  minmax points to 2
- * device floats; qcn_minmax_reset writes [+inf, -inf]. */
+ * device floats; qcn_minmax_reset writes [+inf, -inf].  Subnormals are kept;
+ * a zero result may carry either sign.  NaN input is outside the contract. */
 int qcn_minmax_reset(float* minmax, void* stream);
 int qcn_minmax_f32(const float* x, long long count, float* minmax, void* stream);
 
@@ -104,7 +105,8 @@ int qcn_maxpool2x2_u8_nhwc(const uint8_t* x, int n, int h, int w, int c, uint8_t
                            void* stream);
 
 /* A11 — argmax over the last axis, ties -> lowest index (torch.argmax /
- * topk(1), utils/model_evaluator.py:36,96,160). */
+ * topk(1), utils/model_evaluator.py:36,96,160).  +-inf compare as values;
+ * NaN input is outside the contract. */
 int qcn_argmax_f32(const float* x, int rows, int cols, long long* idx, void* stream);
 
 /* Inference BatchNorm1d (+ReLU) on fp32 [rows, cols] (bn7 of the reference's
@@ -359,10 +361,14 @@ int qcn_conv1x1_join_reduce_u8s8_nhwc(const uint8_t* x, int nimg, int h, int w, 
                                       const float* v2, const float* mult2, const int32_t* corr2, int y2_zp,
                                       int relu2, uint8_t* y2, void* stream);
 /* Residual join (custom_quantization_model.py:94-101 then the next stage's
- * QuantStub): y = quantize(relu?(fp32(sa*(a-za)) + fp32(sb*(b-zb))), s_out, z_out). */
+ * QuantStub): y = quantize(relu?(fp32(sa*(a-za)) + fp32(sb*(b-zb))), s_out, z_out).
+ * Any byte alignment: 16-byte accesses when a, b and y are all 16-byte
+ * aligned, an element-wise path otherwise (same results). */
 int qcn_add_relu_u8(const uint8_t* a, float sa, int za, const uint8_t* b, float sb, int zb,
                     long long count, float s_out, int z_out, int relu, uint8_t* y, void* stream);
-/* nn.MaxPool2d(3, 2, padding=1) on u8 NHWC (c % 16 == 0). */
+/* nn.MaxPool2d(3, 2, padding=1) on u8 NHWC (c % 16 == 0, else
+ * QCN_ERR_UNSUPPORTED).  Any byte alignment: 16-byte accesses when x and y
+ * are 16-byte aligned, a byte-wise kernel otherwise (same results). */
 int qcn_maxpool3x3s2_u8_nhwc(const uint8_t* x, int nimg, int h, int w, int c, uint8_t* y,
                              void* stream);
 /* QuantStub on fp32 NCHW [n][3][h][w] fused with the row im2col of the 7x7 /
@@ -416,8 +422,14 @@ int qcn_qdq_join_f32(const uint8_t* y3, float s3, int z3, const float* a3, const
                      const uint8_t* yd, float sd, int zd, const float* ad, const float* bd,
                      const float* idf, long long count, int c, float* out, float s_next, int z_next,
                      uint8_t* out_q, void* stream);
-/* AdaptiveAvgPool2d(1) on fp32 NHWC: sequential fp32 sum over the window in
- * row-major order, then / (h*w) (ATen's channels-last kernel) -> [n][c]. */
+/* AdaptiveAvgPool2d(1) on fp32 NHWC -> [n][c]: the fp32 sum over the window
+ * in the order of ATen's CPU sum kernel (mean over H, W of a channels-last
+ * map: row-major, 16 pixels at a time into the lowest of four cascade
+ * levels, 2^(ceil_log2(h*w)/4) at a time once that exceeds 16; the plain
+ * sequential sum up to 16 pixels), then / (h*w).  Bit-equal to torch on the CPU where ATen
+ * reduces whole 4-vector column blocks (c % 64 == 0 covers AVX2 and AVX-512);
+ * narrower column remainders take an interleaved order there that depends on
+ * the host's vector width and is not reproduced. */
 int qcn_avgpool_f32_nhwc(const float* x, int n, int h, int w, int c, float* out, void* stream);
 
 #ifdef __cplusplus

@@ -219,8 +219,10 @@ def conv3x3_q(qx, zx, qw, u, v, mult, zp_y, relu):
 
 # -------------------------------------------------------------------------- A10
 def maxpool2x2_nhwc(q):
-    """nn.MaxPool2d(2, 2) — exact in either the u8 or the fp32 domain."""
+    """nn.MaxPool2d(2, 2) — exact in either the u8 or the fp32 domain.  Floor
+    mode: an odd last row / column is dropped."""
     n, h, w, c = q.shape
+    q = q[:, :h // 2 * 2, :w // 2 * 2, :]
     return q.reshape(n, h // 2, 2, w // 2, 2, c).max(axis=(2, 4))
 
 
@@ -246,8 +248,9 @@ def choose_qparams_dynamic(xmin, xmax, qmin=0, qmax=255, reduce_range=True):
     mn = min(F32(xmin), F32(0.0))
     mx = max(F32(xmax), F32(0.0))
     scale = (float(mx) - float(mn)) / (qmax - qmin)
-    if F32(scale) == 0.0 or np.isinf(F32(1.0) / F32(scale)):
-        scale = 0.1
+    with np.errstate(over="ignore"):       # 1 / subnormal overflows on purpose
+        if F32(scale) == 0.0 or np.isinf(F32(1.0) / F32(scale)):
+            scale = 0.1
     small = 6.1e-5
     if scale < float(F32(small)):
         org = scale
@@ -505,7 +508,10 @@ def relu_f32(x):
 
 
 def maxpool3x3s2_f32_nhwc(x):
-    """nn.MaxPool2d(3, 2, padding=1) on fp32 (padding = -inf)."""
+    """nn.MaxPool2d(3, 2, padding=1) on fp32 (padding = -inf).  ATen replaces
+    the running maximum only by a strictly greater value, walking the window
+    in row-major order, so of +0.0 and -0.0 the first one met stays
+    (np.maximum leaves that choice to the host's vector unit)."""
     n, h, w, c = x.shape
     oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     xp = np.full((n, h + 2, w + 2, c), -np.inf, F32)
@@ -513,20 +519,44 @@ def maxpool3x3s2_f32_nhwc(x):
     out = np.full((n, oh, ow, c), -np.inf, F32)
     for r in range(3):
         for s in range(3):
-            out = np.maximum(out, xp[:, r:r + 2 * (oh - 1) + 1:2, s:s + 2 * (ow - 1) + 1:2, :])
+            tap = xp[:, r:r + 2 * (oh - 1) + 1:2, s:s + 2 * (ow - 1) + 1:2, :]
+            out = np.where(tap > out, tap, out)
     return out
 
 
 def avgpool_f32_nhwc(x):
-    """AdaptiveAvgPool2d(1) on an fp32 channels-last map (ATen
-    cpu_adaptive_avg_pool channels-last kernel): sequential fp32 sum over the
-    window in row-major order, then fp32(sum / (H*W))."""
+    """AdaptiveAvgPool2d(1) on an fp32 channels-last map.  ATen computes it as
+    mean over (H, W); its CPU sum kernel (SumKernel.cpp multi_row_sum, the
+    4-vector column blocks of vectorized_outer_sum) adds the window's pixels
+    in row-major order into the lowest of four cascade levels, folds a level
+    into the next one up every 2^lp pixels (lp = max(4, ceil_log2(HW) // 4))
+    and adds the levels lowest first at the end; then fp32(sum / (H*W)).  Up
+    to 16 pixels this is the plain sequential sum.  Pinned against torch at
+    C % 64 == 0 (tests/test_op_edges_cpu.py): column remainders narrower than
+    four vectors take an interleaved order in ATen that depends on the host's
+    vector width and is not restated here."""
     n, h, w, c = x.shape
-    acc = np.zeros((n, c), F32)
-    for i in range(h):
-        for j in range(w):
-            acc = (acc + x[:, i, j, :]).astype(F32)
-    return (acc / F32(h * w)).astype(F32)
+    size = h * w
+    px = np.asarray(x, F32).reshape(n, size, c)
+    lp = max(4, (1 if size <= 2 else int(size - 1).bit_length()) // 4)
+    step, mask = 1 << lp, (1 << lp) - 1
+    acc = [np.zeros((n, c), F32) for _ in range(4)]
+    i = 0
+    while i + step <= size:
+        for _ in range(step):
+            acc[0] = (acc[0] + px[:, i, :]).astype(F32)
+            i += 1
+        for j in range(1, 4):
+            acc[j] = (acc[j] + acc[j - 1]).astype(F32)
+            acc[j - 1] = np.zeros((n, c), F32)
+            if i & (mask << (j * lp)):
+                break
+    while i < size:
+        acc[0] = (acc[0] + px[:, i, :]).astype(F32)
+        i += 1
+    for j in range(1, 4):
+        acc[0] = (acc[0] + acc[j]).astype(F32)
+    return (acc[0] / F32(size)).astype(F32)
 
 
 def _qdq_conv(x_f32, e):

@@ -80,11 +80,12 @@ def test_bad_arguments_return_status(lib):
 
 
 def test_product_fails_loudly_without_library(monkeypatch, tmp_path):
-    """The int8 path has no CPU fallback: a missing .so raises."""
-    import importlib
+    """The int8 path has no CPU fallback: a missing .so raises.  (monkeypatch
+    puts LIB_PATH and the loaded handle back; reloading the module here would
+    leave that handle declared with the previous module's ctypes classes, and
+    every later test in the same process that passes a struct would fail.)"""
     from qconvnet import _lib
     monkeypatch.setattr(_lib, "LIB_PATH", str(tmp_path / "nope.so"))
     monkeypatch.setattr(_lib, "_lib", None)
     with pytest.raises(_lib.QcnError):
         _lib.load()
-    importlib.reload(_lib)
