@@ -2026,6 +2026,11 @@ struct Conv12P {
   static constexpr int OFF_CORR1 = OFF_A1 + 2 * 64 * 16;
   static constexpr int LDS = OFF_CORR1 + 4 * 64;
   static_assert(LDS <= 160 * 1024, "LDS budget");
+  // u8 image input only: the QuantStub table [3][256] (bytes, pre-XORed with
+  // 0x80) behind everything the fp32 form uses
+  static constexpr int OFF_QLUT = LDS;
+  static constexpr int LDS_U8 = OFF_QLUT + 3 * 256;
+  static_assert(OFF_QLUT % 4 == 0 && LDS_U8 <= 160 * 1024, "LDS budget");
 };
 
 // conv_mainloop for weights resident in LDS (same swizzled chunk layout as the
@@ -2103,12 +2108,20 @@ QCN_DEV void c12_stamp(int j, int k) {
 // Images t0, t0 + ts, ... (T / 2 of them, each as its top then its bottom
 // half-image tile) through the producer/consumer pipeline.  512 threads, LDS
 // layout Conv12P.
-QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, int nimg,
+// XT is the input kind.  float: fp32 NCHW, normalised, quantized here with
+// in_inv / in_zp.  uint8_t: raw u8 NHWC images [n][32][32][3]; ToTensor ->
+// Normalize -> quantize_per_tensor is a function of (channel, byte), so the
+// window is staged by lookups in qlut (global [3][256], the QuantStub's
+// output per byte; in_inv is unused).
+template <class XT>
+QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int nimg,
                           float in_inv, int in_zp, const int8_t* __restrict__ w1, ConvEpi ep1,
                           int x2_zp, const int8_t* __restrict__ w2, ConvEpi ep2,
-                          uint8_t* __restrict__ y) {
+                          uint8_t* __restrict__ y, const uint8_t* __restrict__ qlut = nullptr) {
   using C = Conv2Cfg;
   using L = Conv12P;
+  constexpr bool U8 = std::is_same<XT, uint8_t>::value;
+  static_assert(U8 || std::is_same<XT, float>::value, "fp32 NCHW or u8 NHWC input");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool producer = wave >= 4;
@@ -2123,7 +2136,9 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
   uint8_t* in8_0 = lds + L::OFF_IN;
   uint8_t* in8_1 = lds + L::OFF_IN + L::IN8;
 
-  float4 xraw[3];
+  // the staged window row in flight: three float4 (fp32) or the 12 bytes of
+  // four RGB pixels as three dwords (u8)
+  typename std::conditional<U8, uint32_t, float4>::type xraw[3];
   const uint32_t padw = xor80(splat_u8(x2_zp));
   const uint4 pad4 = make_uint4(padw, padw, padw, padw);
   for (int e = tid; e < 2 * C::PROWS * 8; e += 512) {
@@ -2192,6 +2207,9 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
         a1t[i * 64 + lane] = hi ? hi4 : lo4;
       }
     }
+    if constexpr (U8) {   // the QuantStub table, pre-XORed like the window bytes
+      for (int e = tid; e < 3 * 256; e += 512) lds[L::OFF_QLUT + e] = qlut[e] ^ 0x80;
+    }
   };
   // Window staging: the fp32 NCHW input rows of tile t, quantized (aten
   // quantize_per_tensor) to one s8 dword (c0, c1, c2, 0) per pixel.  Window
@@ -2204,6 +2222,14 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
   // values at 4 VALU each (mul, rndne, + zp, saturating v_cvt_pk_u8_f32), one
   // ds_write_b128.  stage_load only issues the loads (their latency hides
   // behind conv1_tile); stage_store quantizes and writes.
+  // u8 input: the same thread owns the same four pixels, 12 contiguous bytes
+  // of the NHWC row (4-byte aligned: 3 * 4g), loaded as three dwords.  The 12
+  // values compile to 12 v_add_u32_sdwa (byte select + table address), 12
+  // ds_read_u8, 8 shifts and 4 v_or3: 2 VALU + 1 LDS read per value instead
+  // of 4 VALU.  A channel's table is 64 dwords over the 32 banks a 4-byte
+  // read sees, so a lookup is 2-way conflicted at the worst (36 wave reads of
+  // <= 4 LDS cycles per tile beside the consumers' ~1,700 cycles of operand
+  // reads).
   // The window index math depends only on the thread id; laundering it
   // through an empty asm per use keeps LICM from hoisting loop-invariant
   // values out of the tile loop (they were spilled: the consumer's MFMA state
@@ -2220,27 +2246,48 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
     const int r = pt < 144 ? pt >> 3 : 0, g = pt & 7;
     const int iy = y0 + (y0 == 0 ? 0 : -2) + r;   // rows 0..17 of the top half, 14..31 of the bottom
     const int nc = n < nimg ? n : nimg - 1;
+    if constexpr (U8) {
+      const uint32_t* p = reinterpret_cast<const uint32_t*>(x + (((long)nc * 32 + iy) * 32 + 4 * g) * 3);
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
-      xraw[c] = *reinterpret_cast<const float4*>(x + (((long)nc * 3 + c) * 32 + iy) * 32 + 4 * g);
+      for (int c = 0; c < 3; ++c) xraw[c] = p[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        xraw[c] = *reinterpret_cast<const float4*>(x + (((long)nc * 3 + c) * 32 + iy) * 32 + 4 * g);
+    }
   };
   auto stage_store = [&](uint8_t* in8, int half) {
     const int pt = fresh_ptid();
     if (pt >= 0 && pt < 144) {
       const int rr = (half ? 0 : 2) + (pt >> 3), g = pt & 7;
-      const float zpf = (float)in_zp;
       uint32_t wd[4];
+      if constexpr (U8) {
+        const uint8_t* lut = lds + L::OFF_QLUT;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        uint32_t d = 0;
+        for (int e = 0; e < 4; ++e) {
+          uint32_t d = 0;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float xv = e == 0 ? xraw[c].x : e == 1 ? xraw[c].y : e == 2 ? xraw[c].z : xraw[c].w;
-          // zp + rint(x / s), saturated to [0, 255]; rint(...) + zp is exact
-          // below 2^24 and saturates the same way above
-          d = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(xv * in_inv) + zpf, c, d);
+          for (int c = 0; c < 3; ++c) {
+            const int k = 3 * e + c;   // byte k of the 12: pixel e, channel c
+            const uint32_t b = (xraw[k >> 2] >> (8 * (k & 3))) & 0xffu;
+            d |= (uint32_t)lut[c * 256 + b] << (8 * c);
+          }
+          wd[e] = d;   // (c0, c1, c2, 0) ^ 0x00808080: the table holds q ^ 0x80
         }
-        wd[e] = d ^ 0x00808080u;
+      } else {
+        const float zpf = (float)in_zp;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          uint32_t d = 0;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float xv = e == 0 ? xraw[c].x : e == 1 ? xraw[c].y : e == 2 ? xraw[c].z : xraw[c].w;
+            // zp + rint(x / s), saturated to [0, 255]; rint(...) + zp is exact
+            // below 2^24 and saturates the same way above
+            d = __builtin_amdgcn_cvt_pk_u8_f32(__builtin_rintf(xv * in_inv) + zpf, c, d);
+          }
+          wd[e] = d ^ 0x00808080u;
+        }
       }
       *reinterpret_cast<uint4*>(in8 + (rr * L::IN_C + 4 + 4 * g) * 4) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
     }
@@ -2450,6 +2497,7 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
 
   if (producer && T > 0) stage_load(tile_of(0));
   setup();
+  if constexpr (U8) __syncthreads();   // the table is written by other threads than read it
   if (producer && T > 0) stage_store(in8_0, 0);
   if (!producer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own weight DMA landed
   __syncthreads();
@@ -2484,6 +2532,10 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const float* __restrict__ x, in
   }
 }
 
+// (QCN_CONV_U8_TU: conv3x3_u8.hip includes this file for the device code and
+// defines the u8-input twins of the kernels that take the fp32 input; the
+// non-template kernels and host functions of this file are left out there.)
+#ifndef QCN_CONV_U8_TU
 __global__ __launch_bounds__(512, 1)
 void conv12p_kernel(const float* __restrict__ x, int nimg, float in_inv, int in_zp,
                     const int8_t* __restrict__ w1, ConvEpi ep1, int x2_zp,
@@ -2491,6 +2543,7 @@ void conv12p_kernel(const float* __restrict__ x, int nimg, float in_inv, int in_
   const int T = (int)blockIdx.x < nimg ? 2 * ((nimg - 1 - (int)blockIdx.x) / (int)gridDim.x + 1) : 0;
   conv12p_body((int)blockIdx.x, (int)gridDim.x, T, x, nimg, in_inv, in_zp, w1, ep1, x2_zp, w2, ep2, y);
 }
+#endif
 
 // --------------------------------------------------------------------------
 // conv1 .. conv6 in ONE persistent launch (r04).  Every conv of the net reads
@@ -2594,6 +2647,7 @@ void convnet_convs16_kernel(const float* __restrict__ x, int nimg, float in_inv,
 // conv12p over the workgroup's image, then the 8-wave conv3+4 and conv5+6
 // pair bodies of the small-batch launches on that image.  Epilogue forms and
 // conv6's layout (ep.kmajor) are runtime here.
+#ifndef QCN_CONV_U8_TU
 __global__ __launch_bounds__(512, 1)
 void convnet_convs_sm_kernel(const float* __restrict__ x, int nimg, float in_inv, QCN_C16_PARAMS,
                              uint8_t* __restrict__ a2, uint8_t* __restrict__ a4, uint8_t* __restrict__ a6) {
@@ -2611,7 +2665,14 @@ void convnet_convs_sm_kernel(const float* __restrict__ x, int nimg, float in_inv
 #endif
   C16_STAMP(3);
 }
+#endif  // QCN_CONV_U8_TU
 
+// Validates the six layers and picks the one-launch form for both input
+// kinds (definition and description with the C ABI below).
+int convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer_t* layers, int kmajor,
+                       ConvnetLayers& L, int& em, int& ncu);
+
+#ifndef QCN_CONV_U8_TU
 // --------------------------------------------------------------------------
 // Generic fallback (any CIN/COUT/H/W, no MFMA): one thread per output element.
 // Used only for shapes without a tuned instantiation (unit tests, odd sizes).
@@ -2745,6 +2806,7 @@ void set_qdq(ConvEpi& ep, const qcn_qdq_t* q) {
   next = (next + 1) % 16;
   if (ncache < 16) ++ncache;
 }
+#endif  // QCN_CONV_U8_TU
 
 }  // namespace qcn
 
@@ -3107,12 +3169,12 @@ int qcn_conv12_fused_f32_nchw(const float* x, int nimg, float in_scale, int in_z
 
 }  // extern "C"
 
-namespace {
-// The form qcn_convnet_convs_f32_nchw takes (shared with the host query
-// qcn_convnet_convs_form): fills L and the epilogue mode em and returns 1 (one
-// image per workgroup), 2 (persistent) or the error the launch returns.
-int convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer_t* layers, int kmajor,
-                       qcn::ConvnetLayers& L, int& em, int& ncu) {
+// The form qcn_convnet_convs_f32_nchw and qcn_convnet_convs_u8_nhwc take
+// (shared with the host query qcn_convnet_convs_form): fills L and the
+// epilogue mode em and returns 1 (one image per workgroup), 2 (persistent) or
+// the error the launch returns.
+int qcn::convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer_t* layers, int kmajor,
+                            qcn::ConvnetLayers& L, int& em, int& ncu) {
   if (!layers) return QCN_ERR_ARG;
   if (nimg <= 0 || in_zp < 0 || in_zp > 255 || !(in_scale > 0.f)) return QCN_ERR_ARG;
   L = qcn::ConvnetLayers{};
@@ -3147,7 +3209,6 @@ int convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer
   else return QCN_ERR_UNSUPPORTED;
   return 2;
 }
-}  // namespace
 
 extern "C" {
 

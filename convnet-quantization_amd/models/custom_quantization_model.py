@@ -51,15 +51,17 @@ class CustomQuantizationModel(nn.Module):
         self.model.load_state_dict(load_checkpoint_state(state_dict))
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
-                 max_batches=None, observer="minmax"):
+                 max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD):
         """observer: "minmax" (default) or "histogram" (torch.ao's default
-        HistogramObserver on every stub, reduce_range=False)."""
+        HistogramObserver on every stub, reduce_range=False).  ``mean`` /
+        ``std``: the Normalize constants applied to raw uint8 NHWC images."""
         self.model.eval()
         folded = fold_state_dict(self.model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)
-        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="qdq")
+        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="qdq",
+                           mean=mean, std=std)
         spec = build_qspec(folded, ranges, "qdq", per_channel)
-        self.quantized_model = QuantizedConvNet(spec, self.device)
+        self.quantized_model = QuantizedConvNet(spec, self.device, mean=mean, std=std)
         return self.quantized_model
 
     def forward(self, x):
@@ -86,7 +88,8 @@ class CustomQuantizedResNet50(nn.Module):
     their float-domain residual add, avgpool and fc — as the static int8
     MI355X executor ``qconvnet.resnet.QuantizedResNet`` (BN folded, per-channel
     s8 weights, MinMax-calibrated u8 activations).  ``calibration_batches``:
-    an iterable of fp32 [N,3,H,W] tensors (or (x, y) pairs); default 32
+    an iterable of fp32 [N,3,H,W] tensors or raw uint8 [N,H,W,3] images,
+    normalised with ``mean`` / ``std`` (or (x, y) pairs); default 32
     synthetic ImageNet-normalised 224x224 images.  ``conv1_scale`` is accepted
     for signature compatibility; the reference never uses it.
 
@@ -97,7 +100,7 @@ class CustomQuantizedResNet50(nn.Module):
     as ``qconvnet.resnet_qdq.QuantizedResNetQDQ``."""
 
     def __init__(self, model, conv1_scale=1.0, calibration_batches=None, device="cuda",
-                 per_channel=True, mode="static"):
+                 per_channel=True, mode="static", mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD):
         from qconvnet.resnet import quantize_resnet
         from qconvnet.resnet_qdq import quantize_resnet_reference
         from models.resnet import synthetic_images
@@ -110,7 +113,7 @@ class CustomQuantizedResNet50(nn.Module):
         self.conv1_scale = conv1_scale
         self.mode = mode
         build = quantize_resnet if mode == "static" else quantize_resnet_reference
-        self.quantized_model = build(model.eval(), batches, device, per_channel)
+        self.quantized_model = build(model.eval(), batches, device, per_channel, mean=mean, std=std)
 
     def forward(self, x):
         return self.quantized_model(x)

@@ -27,16 +27,21 @@ import torch.nn.functional as F
 from models.baseline_model import CONV_TABLE, SimpleConvNet, load_checkpoint_state
 from qconvnet import ops
 from qconvnet import quant as Q
-from qconvnet.qmodel import cuda_device, fold_state_dict
+from qconvnet.data import CIFAR_MEAN, CIFAR_STD
+from qconvnet.qmodel import cuda_device, fold_state_dict, normalized_input
 
 F32 = np.float32
 
 
 class DynamicQuantConvNet:
-    """fp32 convs (+ optional BN fold) and dynamic-int8 fc1/fc2 on the GPU."""
+    """fp32 convs (+ optional BN fold) and dynamic-int8 fc1/fc2 on the GPU.
+    Raw uint8 NHWC images are normalised with ``mean`` / ``std`` on the device
+    (ops.normalize_u8)."""
 
-    def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True):
+    def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
+                 std=CIFAR_STD):
         self.device = cuda_device(device)
+        self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.reduce_range = reduce_range
         self.sharded = False   # True: batch-exact across ranks (see _range)
         self.quantized = True
@@ -113,7 +118,7 @@ class DynamicQuantConvNet:
 
     def _forward(self, x):
         host = not x.is_cuda
-        x = x.to(self.device, torch.float32)
+        x = normalized_input(x, self.device, self.ntab)
         y = self.classify(self.features(x))
         if host or self.host_io:
             return y.cpu()
@@ -169,10 +174,12 @@ class DynamicPTQModel:
     def __call__(self, x):
         return self.forward(x)
 
-    def quantize(self):
+    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD):
+        """``mean`` / ``std``: the Normalize constants applied to raw uint8
+        NHWC images."""
         self.fp32_model = self.fp32_model.cpu().eval()
         self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=True,
-                                                   device=self.device)
+                                                   device=self.device, mean=mean, std=std)
         return self.quantized_model
 
     def get_model_size(self):

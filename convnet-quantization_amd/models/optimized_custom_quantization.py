@@ -36,15 +36,18 @@ import torch.nn.functional as F
 from models.resnet import resnet50
 from qconvnet import ops
 from qconvnet import quant as Q
-from qconvnet.qmodel import cuda_device
+from qconvnet.data import IMAGENET_MEAN, IMAGENET_STD
+from qconvnet.qmodel import cuda_device, normalized_input
 from qconvnet.resnet import _fold, _np
 
 
 class DynamicFcResNet:
     """Fused fp32 ResNet body on the GPU + dynamic int8 fc (HIP)."""
 
-    def __init__(self, model, device="cuda", reduce_range=True):
+    def __init__(self, model, device="cuda", reduce_range=True, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.device = cuda_device(device)
+        # raw uint8 NHWC images are normalised on the device (ops.normalize_u8)
+        self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.reduce_range = reduce_range
         self.quantized = True
         self.is_custom_quantized = True
@@ -99,7 +102,7 @@ class DynamicFcResNet:
     def __call__(self, x):
         host = not x.is_cuda
         with torch.cuda.device(self.device):
-            y = self.classify(self.features(x.to(self.device, torch.float32)))
+            y = self.classify(self.features(normalized_input(x, self.device, self.ntab)))
             if host or self.host_io:
                 return y.cpu()
             torch.cuda.current_stream(self.device).synchronize()
@@ -145,9 +148,9 @@ class OptimizedCustomQuantization:
         except _lib.QcnError as e:   # the reference raises when no engine exists (:17-22)
             raise RuntimeError("No supported quantization engine found: " + str(e)) from e
 
-    def quantize(self, model):
+    def quantize(self, model, mean=IMAGENET_MEAN, std=IMAGENET_STD):
         model = model.cpu().eval()
-        self.quantized_model = DynamicFcResNet(model, self.device)
+        self.quantized_model = DynamicFcResNet(model, self.device, mean=mean, std=std)
         return self.quantized_model
 
     def get_model_size(self, model):

@@ -39,23 +39,26 @@ class StaticPTQModel:
         self.fp32_model.load_state_dict(load_checkpoint_state(state_dict))
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
-                 max_batches=None, observer="minmax"):
+                 max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD):
         """Calibrate (fp32, BN folded — the reference quantizes on the CPU, so
         does the default here) and build the int8 GPU model.  observer:
         "minmax" (default) or "histogram", torch.ao's default
         HistogramObserver (get_default_qconfig('fbgemm') activations,
-        reduce_range=False)."""
+        reduce_range=False).  ``mean`` / ``std``: the Normalize constants
+        applied to raw uint8 NHWC images (calibration batches and inference
+        inputs may be either those or normalised fp32 NCHW)."""
         self.fp32_model.eval()
         if self.mode == "reference":
             from models.dynamic_ptq_model import DynamicQuantConvNet
             self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=False,
-                                                       device=self.device)
+                                                       device=self.device, mean=mean, std=std)
             return self.quantized_model
         folded = fold_state_dict(self.fp32_model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)
-        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="static")
+        ranges = calibrate(folded, batches, calibration_device, observer=observer, mode="static",
+                           mean=mean, std=std)
         spec = build_qspec(folded, ranges, "static", per_channel)
-        self.quantized_model = QuantizedConvNet(spec, self.device)
+        self.quantized_model = QuantizedConvNet(spec, self.device, mean=mean, std=std)
         return self.quantized_model
 
     def get_model_size(self, model):

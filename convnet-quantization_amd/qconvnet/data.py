@@ -52,7 +52,9 @@ def synthetic_task(n, seed, hw=32, noise=1.3):
 
 def calibration_batches(loader=None, max_batches=None, default_images=512, default_seed=1):
     """Images from a reference-style loader ((images, labels) batches), a
-    tensor, or — when None — the first 512 synthetic images of seed 1."""
+    tensor, or — when None — the first 512 synthetic images of seed 1.
+    Batches pass through as they are: normalised fp32 NCHW or raw uint8 NHWC
+    (the calibrate functions normalise the latter themselves)."""
     if loader is None:
         return [torch.from_numpy(synthetic_images(default_images, default_seed))]
     if torch.is_tensor(loader):

@@ -248,6 +248,80 @@ def conv12_fused(x, in_scale, in_zp, l1, l2, out=None):
     return out
 
 
+# ------------------------------------------------------ raw u8 image input
+def _u8_images(x, name, hw=None):
+    """A device u8 NHWC batch the kernels can read: checked for layout, made
+    contiguous, and moved to a 4-byte boundary when ``hw`` (the conv entries'
+    fixed size) is given."""
+    from .quant import check_u8_images
+    if not x.is_cuda:
+        raise ValueError(f"{name}: expected a device tensor")
+    check_u8_images(x, hw)
+    x = x.contiguous()
+    if hw is not None and x.data_ptr() % 4:
+        x = x.clone()
+    return x
+
+
+def normalize_u8(img, ntab, out=None):
+    """u8 NHWC [n,h,w,3] -> fp32 NCHW [n,3,h,w], out = ntab[c][img]
+    (qcn_u8img_normalize_f32_nchw).  ``ntab``: device float32 [3,256] from
+    quant.normalize_table.  Any h, w and any byte alignment of ``img``."""
+    img = _u8_images(img, "normalize_u8.img")
+    _need(ntab, torch.float32, "normalize_u8.ntab")
+    if ntab.numel() != 768:
+        raise ValueError("normalize_u8.ntab: expected [3, 256]")
+    n, h, w, _ = img.shape
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=img.device)
+    _need(out, torch.float32, "normalize_u8.out")
+    if out.numel() != img.numel():
+        raise ValueError("normalize_u8.out: expected [n, 3, h, w]")
+    if n:
+        check(lib().qcn_u8img_normalize_f32_nchw(_ptr(img), n, h, w, _ptr(ntab), _ptr(out), _stream()),
+              "normalize_u8")
+    return out
+
+
+def _need_qlut(qlut, name):
+    _need(qlut, torch.uint8, name)
+    if qlut.numel() != 768:
+        raise ValueError(f"{name}: expected [3, 256]")
+
+
+def conv12_fused_u8(img, qlut, in_zp, l1, l2, out=None):
+    """conv12_fused() on raw images: ``img`` u8 NHWC [n,32,32,3], ``qlut`` the
+    device uint8 [3,256] QuantStub table (quant.quantize_table).  The result
+    equals conv12_fused() of the table-expanded input bit for bit."""
+    img = _u8_images(img, "conv12_u8.img", 32)
+    _need_qlut(qlut, "conv12_u8.qlut")
+    n = img.shape[0]
+    if out is None:
+        out = torch.empty((n, 16, 16, 64), dtype=torch.uint8, device=img.device)
+    q1 = C.byref(l1.qdq) if l1.qdq is not None else None
+    q2 = C.byref(l2.qdq) if l2.qdq is not None else None
+    check(lib().qcn_conv12_fused_u8_nhwc(
+        _ptr(img), n, _ptr(qlut), int(in_zp), _ptr(l1.w), _ptr(l1.u), _ptr(l1.v), _ptr(l1.mult),
+        _ptr(l1.corr), int(l1.z_y), int(bool(l1.relu)), q1, int(l2.z_x), _ptr(l2.w), _ptr(l2.u),
+        _ptr(l2.v), _ptr(l2.mult), _ptr(l2.corr), int(l2.z_y), int(bool(l2.relu)), q2, _ptr(out),
+        _stream()), "conv12_fused_u8")
+    return out
+
+
+def convnet_convs_u8(img, qlut, in_zp, layers, a2, a4, a6, kmajor=True):
+    """convnet_convs() on raw images (``img``, ``qlut`` as for
+    conv12_fused_u8): the same forms by batch, False where convnet_convs()
+    returns False."""
+    img = _u8_images(img, "convnet_convs_u8.img", 32)
+    _need_qlut(qlut, "convnet_convs_u8.qlut")
+    rc = lib().qcn_convnet_convs_u8_nhwc(_ptr(img), img.shape[0], _ptr(qlut), int(in_zp), layers,
+                                         _ptr(a2), _ptr(a4), _ptr(a6), int(bool(kmajor)), _stream())
+    if rc == _lib.QCN_ERR_UNSUPPORTED:
+        return False
+    check(rc, "convnet_convs_u8")
+    return True
+
+
 def conv_layers(layers, in_zp):
     """The six conv layers of SimpleConvNet (objects with w, u, v, mult, corr,
     z_x, z_y, relu, qdq) as the qcn_conv_layer_t array convnet_convs() takes.

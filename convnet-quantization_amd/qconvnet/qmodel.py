@@ -30,6 +30,7 @@ import torch.nn.functional as F
 
 from . import ops
 from . import quant as Q
+from .data import CIFAR_MEAN, CIFAR_STD
 
 F32 = np.float32
 CONV_TABLE = ((3, 64, False), (64, 64, True), (64, 128, False), (128, 128, True),
@@ -52,6 +53,24 @@ def fold_state_dict(sd):
     out["fc2.w"] = np.asarray(g["fc2.weight"], F32)
     out["fc2.b"] = np.asarray(g["fc2.bias"], F32)
     return out
+
+
+# ============================================================ raw u8 input
+def normalized_input(x, device, ntab):
+    """The fp32 NCHW tensor a model consumes, on ``device``.  fp32 input is
+    moved as it is.  A uint8 batch must be NHWC [N,H,W,3] (ValueError
+    otherwise — raw bytes are never cast to float); its bytes are moved and
+    then expanded through ``ntab`` (Q.normalize_table): by the HIP kernel on
+    the GPU, by indexing on the CPU, both bit-equal to ToTensor + Normalize."""
+    dev = torch.device(device)
+    if x.dtype != torch.uint8:
+        return x.to(dev, torch.float32)
+    Q.check_u8_images(x)
+    x = x.to(dev)
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            return ops.normalize_u8(x, ntab.to(dev))
+    return Q.expand_u8(x, ntab)
 
 
 # ============================================================ calibration
@@ -117,10 +136,14 @@ def _observed_names(mode):
     raise ValueError(f"unknown mode {mode!r}")
 
 
-def calibrate(folded, batches, device="cpu", observer="minmax", mode=None):
+def calibrate(folded, batches, device="cpu", observer="minmax", mode=None, mean=CIFAR_MEAN,
+              std=CIFAR_STD):
     """Run the BN-folded fp32 net over calibration batches and record the
     range of every observer ``mode`` needs ("static", "qdq"; None: those of
-    both) as {name: (lo, hi)} for build_qspec.
+    both) as {name: (lo, hi)} for build_qspec.  Batches are normalised fp32
+    NCHW, or raw uint8 NHWC [N,32,32,3] images, normalised here with
+    ``mean`` / ``std`` (the ranges equal those of the fp32-fed calibration
+    bit for bit).
 
     observer="minmax" (default): the running min/max.  observer="histogram":
     torch.ao's default HistogramObserver (2048 bins, reduce_range=False); the
@@ -140,6 +163,7 @@ def calibrate(folded, batches, device="cpu", observer="minmax", mode=None):
     dev = torch.device(device)
     t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in folded.items()}
     rng = {n: _OBSERVERS[observer](dev) for n in names}
+    ntab = Q.normalize_table(mean, std).to(dev)
 
     def see(name, x):
         if name in rng:
@@ -147,7 +171,7 @@ def calibrate(folded, batches, device="cpu", observer="minmax", mode=None):
 
     with torch.no_grad():
         for xb in batches:
-            x = xb.to(dev, torch.float32)
+            x = normalized_input(xb, dev, ntab)
             see("x", x)
             for i, (_, _, pool) in enumerate(CONV_TABLE, start=1):
                 see(f"conv{i}_in", x)
@@ -271,10 +295,16 @@ class _DevLayer:
 
 class QuantizedConvNet:
     """Duck-typed int8 model object (the surface of the reference's models.*:
-    eval(), to() in place, cpu(), __call__; fp32 [N,3,32,32] in, fp32 [N,10] out)."""
+    eval(), to() in place, cpu(), __call__; fp32 [N,3,32,32] in, fp32 [N,10] out).
 
-    def __init__(self, spec, device="cuda", fuse12=True):
+    Raw images are accepted too: a uint8 NHWC batch [N,32,32,3] is normalised
+    with ``mean`` / ``std`` and quantized by table lookups inside the conv1+conv2
+    stage (a quarter of the input bytes, no host preprocessing); the logits
+    equal those of the normalised fp32 batch bit for bit."""
+
+    def __init__(self, spec, device="cuda", fuse12=True, mean=CIFAR_MEAN, std=CIFAR_STD):
         self.spec = spec
+        self.mean, self.std = tuple(mean), tuple(std)
         self.mode = spec["mode"]
         self.device = cuda_device(device)
         self.quantized = True
@@ -326,6 +356,11 @@ class QuantizedConvNet:
             self.in_scale, self.in_zp = sp["in"]
         else:
             self.in_scale, self.in_zp = sp["conv1"]["s_x"], sp["conv1"]["z_x"]
+        # u8 image input: ToTensor + Normalize per (channel, byte), and the
+        # QuantStub of that with the input qparams
+        ntab = Q.normalize_table(self.mean, self.std)
+        self.ntab = ntab.to(self.device)
+        self.qlut = Q.quantize_table(ntab, self.in_scale, self.in_zp).to(self.device)
         perm = Q.nhwc_flatten_perm()
         for name in ("fc1", "fc2"):
             e = sp[name]
@@ -413,7 +448,8 @@ class QuantizedConvNet:
         return self._head_fused(n) and (self.mode != "qdq" or self._pairs(keep))
 
     def _fused(self, x_shape):
-        return self.fuse12 and tuple(x_shape[1:]) == (3, 32, 32)
+        # fp32 NCHW or raw u8 NHWC images
+        return self.fuse12 and tuple(x_shape[1:]) in ((3, 32, 32), (32, 32, 3))
 
     def _convs_form(self, n, keep=False):
         """Whether the library takes the one-launch convs at batch n: what a
@@ -449,9 +485,13 @@ class QuantizedConvNet:
         Returns the fp32 logits tensor (a reused buffer); with keep=True also
         the dict of intermediate u8 activations.  ``marks``: a list that
         receives one timing event before the first launch and one after each
-        launch named by kernel_names(x.shape)."""
+        launch named by kernel_names(x.shape).  ``x``: fp32 NCHW
+        [N,3,32,32], or raw uint8 NHWC [N,32,32,3] images."""
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
+        if x.dtype == torch.uint8:
+            Q.check_u8_images(x, 32)
+            x = x.contiguous()
         with torch.cuda.device(self.device):   # ops launch on this device's current stream
             return self._run(x, keep, marks, slot)
 
@@ -469,12 +509,20 @@ class QuantizedConvNet:
         mark()
         d = L[0]
         names = ["a2", "a3", "a4", "a5", "a6"]
+        u8 = x.dtype == torch.uint8
+
+        def conv12():
+            if u8:
+                ops.conv12_fused_u8(x, self.qlut, self.in_zp, L[0], L[1], out=b["a2"])
+            else:
+                ops.conv12_fused(x, self.in_scale, self.in_zp, L[0], L[1], out=b["a2"])
+
         head = self._head(n, keep)
         convs_done = conv12_done = False
         if self._w4(x.shape, keep):
             if self._conv_layers is None:
                 self._conv_layers = ops.conv_layers(L, self.in_zp)
-            ops.conv12_fused(x, self.in_scale, self.in_zp, L[0], L[1], out=b["a2"])
+            conv12()
             mark()
             if head and "a6k" not in b:
                 b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
@@ -491,8 +539,13 @@ class QuantizedConvNet:
                 b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
             if self._conv_layers is None:
                 self._conv_layers = ops.conv_layers(L, self.in_zp)
-            convs_done = ops.convnet_convs(x, self.in_scale, self.in_zp, self._conv_layers, b["a2"],
-                                           b["a4"], b["a6k"] if head else b["a6"], kmajor=head)
+            out6 = b["a6k"] if head else b["a6"]
+            if u8:
+                convs_done = ops.convnet_convs_u8(x, self.qlut, self.in_zp, self._conv_layers, b["a2"],
+                                                  b["a4"], out6, kmajor=head)
+            else:
+                convs_done = ops.convnet_convs(x, self.in_scale, self.in_zp, self._conv_layers, b["a2"],
+                                               b["a4"], out6, kmajor=head)
             self._convs_ok[n] = convs_done
             if convs_done:
                 mark()
@@ -500,10 +553,14 @@ class QuantizedConvNet:
         if convs_done or conv12_done:
             pass
         elif self._fused(x.shape):
-            ops.conv12_fused(x, self.in_scale, self.in_zp, L[0], L[1], out=b["a2"])
+            conv12()
             mark()
             prev, first = b["a2"], 2
         else:
+            if u8:   # the stand-alone conv1 has no u8 stage: normalise first
+                if "xf" not in b:
+                    b["xf"] = torch.empty((n, 3, 32, 32), dtype=torch.float32, device=self.device)
+                x = ops.normalize_u8(x, self.ntab, out=b["xf"])
             ops.conv1_f32(x, self.in_scale, self.in_zp, d.w, d.u, d.v, d.mult, d.corr, d.z_y,
                           d.relu, d.qdq, out=b["a1"])
             mark()
@@ -615,7 +672,11 @@ class QuantizedConvNet:
     @torch.no_grad()
     def forward(self, x):
         host = not x.is_cuda
-        xd = x.to(self.device, torch.float32, non_blocking=False).contiguous()
+        if x.dtype == torch.uint8:   # raw images: the bytes go to the device as they are
+            Q.check_u8_images(x, 32)
+            xd = x.to(self.device, non_blocking=False).contiguous()
+        else:
+            xd = x.to(self.device, torch.float32, non_blocking=False).contiguous()
         out = self.run(xd).clone()
         if host or self.host_io:
             return out.cpu()

@@ -14,6 +14,9 @@ vectors in tests/golden/ pin it; tests/test_host_quant.py checks it):
 * quantize_weight — the weight quantization done by from_float;
 * epilogue_constants — FBGEMM ReQuantizeOutput's fp32 constants
   (torch/include/fbgemm/OutputProcessing-inl.h:76-127, vector form);
+* normalize_table / quantize_table / expand_u8 — ToTensor + Normalize (+
+  aten quantize_per_tensor) of a raw uint8 image as 3 x 256 tables
+  (tests/test_u8_input_cpu.py checks them against torch);
 * hist_combine / hist_upscale / hist_param_search / hist_quantization_error and
   HistogramState — HistogramObserver's host half (torch/ao/quantization/
   observer.py:1076-1370).  These are built from torch CPU ops in torch's own
@@ -138,6 +141,53 @@ def nhwc_flatten_perm(c=256, h=4, w=4):
     pooled tensor while keeping baseline_model.py:78's NCHW flatten semantics."""
     idx = np.arange(c * h * w).reshape(c, h, w)
     return np.ascontiguousarray(np.transpose(idx, (1, 2, 0))).reshape(-1)
+
+
+# ------------------------------------------------------ raw u8 image input
+# ToTensor -> Normalize -> QuantStub of a u8 HWC image is a function of
+# (channel, byte): two 3 x 256 tables replace the per-pixel arithmetic, exact
+# by construction (tests/test_u8_input_cpu.py checks both against torch).
+U8_LAYOUT = "uint8 images are expected as NHWC [N, H, W, 3]"
+
+
+def normalize_table(mean, std):
+    """float32 [3, 256]: tab[c][p] = (fp32(p) / 255 - mean_c) / std_c, with
+    torch's fp32 ops in the order ToTensor (div 255) then Normalize (sub, div)."""
+    mean = torch.as_tensor(mean, dtype=torch.float32).reshape(3, 1)
+    std = torch.as_tensor(std, dtype=torch.float32).reshape(3, 1)
+    p = torch.arange(256, dtype=torch.float32).reshape(1, 256).div(255)
+    return p.sub(mean).div(std).contiguous()
+
+
+def quantize_table(tab, scale, zp):
+    """uint8 [3, 256]: aten quantize_per_tensor of the normalised table,
+    clamp(zp + rint(x * fp32(1 / scale)), 0, 255)."""
+    x = np.asarray(tab, F32)
+    inv = F32(F32(1.0) / F32(scale))
+    q = np.rint((x * inv).astype(F32)).astype(np.int64) + int(zp)
+    return torch.from_numpy(np.clip(q, 0, 255).astype(np.uint8))
+
+
+def check_u8_images(x, hw=None):
+    """Raise unless x is a uint8 NHWC image batch [N, H, W, 3] (H = W = hw when
+    given).  An NCHW u8 batch is rejected, not guessed at."""
+    shape = tuple(x.shape)
+    ok = x.dtype == torch.uint8 and len(shape) == 4 and shape[3] == 3
+    if ok and hw is not None:
+        ok = shape[1:3] == (hw, hw)
+    if not ok:
+        want = f"[N, {hw}, {hw}, 3]" if hw is not None else "[N, H, W, 3]"
+        raise ValueError(f"{U8_LAYOUT}; expected {want}, got {x.dtype} {list(shape)}")
+
+
+def expand_u8(x, ntab):
+    """Host form of the normalize kernel: u8 NHWC [N, H, W, 3] -> fp32 NCHW
+    [N, 3, H, W] by indexing ntab (normalize_table); equals ToTensor +
+    Normalize of the same bytes bit for bit."""
+    check_u8_images(x)
+    idx = x.permute(0, 3, 1, 2).long()
+    tab = torch.as_tensor(ntab, dtype=torch.float32, device=x.device)
+    return torch.stack([tab[c][idx[:, c]] for c in range(3)], dim=1).contiguous()
 
 
 # ------------------------------------------------------ HistogramObserver (host)

@@ -27,7 +27,8 @@ import torch.nn.functional as F
 
 from . import ops
 from . import quant as Q
-from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device
+from .data import IMAGENET_MEAN, IMAGENET_STD
+from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device, normalized_input
 
 F32 = np.float32
 
@@ -67,8 +68,10 @@ def fold_state_dict(sd):
 
 
 # ============================================================ calibration
-def calibrate(folded, batches, device="cpu"):
-    """fp32 forward of the folded net recording every observer's range:
+def calibrate(folded, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """fp32 forward of the folded net recording every observer's range
+    (batches: normalised fp32 NCHW, or raw uint8 NHWC images normalised here
+    with ``mean`` / ``std``):
     x, stem (post-ReLU), per block c1/c2 (post-ReLU), c3 and ds (pre-add),
     out (post add+ReLU), fc.  On the CPU (the default) the ranges are those
     torch.ao's observers record on the same host (same fp32 ops, same folded
@@ -83,12 +86,13 @@ def calibrate(folded, batches, device="cpu"):
     blocks = [{k: (t(v[0]), t(v[1]), v[2], v[3]) for k, v in b.items()} for b in folded["blocks"]]
     fc = [t(a) for a in folded["fc"]]
     rng = {"x": _Range(dev), "stem": _Range(dev), "fc": _Range(dev)}
+    ntab = Q.normalize_table(mean, std).to(dev)
     for i, b in enumerate(blocks):
         for k in list(b) + ["out"]:
             rng[f"b{i}.{k}"] = _Range(dev)
     with torch.no_grad():
         for xb in batches:
-            x = xb.to(dev, torch.float32)
+            x = normalized_input(xb, dev, ntab)
             rng["x"](x)
             x = F.relu(F.conv2d(x, stem[0], stem[1], stride=2, padding=3))
             rng["stem"](x)
@@ -151,22 +155,27 @@ def build_spec(folded, ranges, per_channel=True):
     return spec
 
 
-def quantize_resnet(model, calib_batches, device="cuda", per_channel=True, calibration_device="cpu"):
+def quantize_resnet(model, calib_batches, device="cuda", per_channel=True, calibration_device="cpu",
+                    mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """fp32 ResNet (models.resnet / torchvision layout) -> QuantizedResNet on
-    `device`; calibration runs on `calibration_device` (CPU: deterministic)."""
+    `device`; calibration runs on `calibration_device` (CPU: deterministic).
+    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference)."""
     folded = fold_state_dict(model.state_dict())
-    ranges = calibrate(folded, calib_batches, calibration_device)
-    return QuantizedResNet(build_spec(folded, ranges, per_channel), device)
+    ranges = calibrate(folded, calib_batches, calibration_device, mean, std)
+    return QuantizedResNet(build_spec(folded, ranges, per_channel), device, mean, std)
 
 
 # ============================================================ device model
 class QuantizedResNet:
     """Duck-typed int8 ResNet (eval / cpu / to / __call__ like the reference's
-    models.*): fp32 [N,3,H,W] in, fp32 [N,num_classes] logits out."""
+    models.*): fp32 [N,3,H,W] in, fp32 [N,num_classes] logits out.  Raw uint8
+    NHWC images [N,H,W,3] are normalised with ``mean`` / ``std`` on the device
+    first (ops.normalize_u8; the stem itself reads fp32)."""
 
-    def __init__(self, spec, device="cuda"):
+    def __init__(self, spec, device="cuda", mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.spec = spec
         self.device = cuda_device(device)
+        self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.quantized = True
         self.host_io = False
         self._graphs = {}
@@ -261,7 +270,7 @@ class QuantizedResNet:
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
-            return self._run(x, keep, marks)
+            return self._run(normalized_input(x, self.device, self.ntab), keep, marks)
 
     def _run(self, x, keep, marks):
         g = self._steps(x, keep, marks)
@@ -280,6 +289,7 @@ class QuantizedResNet:
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
+            x = normalized_input(x, self.device, self.ntab)
             main = torch.cuda.current_stream(self.device)
             if len(getattr(self, "_side", ())) < nsplit:
                 self._side = [torch.cuda.Stream(device=self.device) for _ in range(nsplit)]
@@ -400,7 +410,8 @@ class QuantizedResNet:
     @torch.no_grad()
     def forward(self, x):
         host = not x.is_cuda
-        xd = x.to(self.device, torch.float32).contiguous()
+        # (raw uint8 images: the bytes are moved, then normalised on the device)
+        xd = normalized_input(x, self.device, self.ntab).contiguous()
         # two interleaved stream slices fill each layer's last workgroup round
         # (+6 % at batch 512, profiles/r02_diag_resnet_streams.txt)
         out = self.run_streams(xd, 2) if xd.shape[0] >= 128 else self.run(xd).clone()

@@ -34,7 +34,8 @@ import torch.nn.functional as F
 
 from . import ops
 from . import quant as Q
-from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device
+from .data import IMAGENET_MEAN, IMAGENET_STD
+from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device, normalized_input
 
 F32 = np.float32
 
@@ -68,12 +69,15 @@ def unfolded_state(sd):
     return out
 
 
-def calibrate(net, batches, device="cpu"):
+def calibrate(net, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
     """The observers of the live-stub model: fp32 forward of the unfolded net
     (torch's own conv / batch_norm / pooling ops, as torch.ao's prepared model
     runs during calibration) recording, per int8 op, its QuantStub's input
-    range ("<name>.in") and its output range ("<name>.out")."""
+    range ("<name>.in") and its output range ("<name>.out").  Batches:
+    normalised fp32 NCHW, or raw uint8 NHWC images normalised here with
+    ``mean`` / ``std``."""
     dev = torch.device(device)
+    ntab = Q.normalize_table(mean, std).to(dev)
 
     def t(a):
         return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -94,7 +98,7 @@ def calibrate(net, batches, device="cpu"):
 
     with torch.no_grad():
         for xb in batches:
-            x = xb.to(dev, torch.float32)
+            x = normalized_input(xb, dev, ntab)
             x = F.max_pool2d(F.relu(qconv("stem", x, net["stem"])), 3, 2, 1)
             for i, blk in enumerate(net["blocks"]):
                 out = F.relu(qconv(f"b{i}.c1", x, blk["c1"]))
@@ -135,20 +139,24 @@ def build_spec(net, ranges, per_channel=True):
 
 
 def quantize_resnet_reference(model, calib_batches, device="cuda", per_channel=True,
-                              calibration_device="cpu"):
-    """fp32 ResNet (torchvision layout) -> QuantizedResNetQDQ on `device`."""
+                              calibration_device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """fp32 ResNet (torchvision layout) -> QuantizedResNetQDQ on `device`.
+    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference)."""
     net = unfolded_state(model.state_dict())
-    ranges = calibrate(net, calib_batches, calibration_device)
-    return QuantizedResNetQDQ(build_spec(net, ranges, per_channel), device)
+    ranges = calibrate(net, calib_batches, calibration_device, mean, std)
+    return QuantizedResNetQDQ(build_spec(net, ranges, per_channel), device, mean, std)
 
 
 class QuantizedResNetQDQ:
     """Duck-typed live-stub int8 ResNet (eval / cpu / to / __call__): fp32
-    [N,3,H,W] in, fp32 [N,num_classes] logits out."""
+    [N,3,H,W] in, fp32 [N,num_classes] logits out.  Raw uint8 NHWC images
+    [N,H,W,3] are normalised with ``mean`` / ``std`` on the device first
+    (ops.normalize_u8)."""
 
-    def __init__(self, spec, device="cuda"):
+    def __init__(self, spec, device="cuda", mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.spec = spec
         self.device = cuda_device(device)
+        self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.quantized = True
         self.host_io = False
         self._upload()
@@ -199,7 +207,7 @@ class QuantizedResNetQDQ:
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
-            return self._run(x, keep)
+            return self._run(normalized_input(x, self.device, self.ntab), keep)
 
     def _run(self, x, keep):
         inter = {}
@@ -240,7 +248,7 @@ class QuantizedResNetQDQ:
     @torch.no_grad()
     def forward(self, x):
         host = not x.is_cuda
-        xd = x.to(self.device, torch.float32).contiguous()
+        xd = normalized_input(x, self.device, self.ntab).contiguous()
         out = self.run(xd).clone()
         if host or self.host_io:
             return out.cpu()

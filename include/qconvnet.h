@@ -199,6 +199,38 @@ int qcn_conv12_fused_f32_nchw(const float* x, int nimg, float in_scale, int in_z
                               const int32_t* corr2, int y_zp, int relu2, const qcn_qdq_t* qdq2,
                               uint8_t* y, void* stream);
 
+/* ---- raw u8 image input ------------------------------------------------
+ * ToTensor -> Normalize(mean, std) -> QuantStub is a function of (channel,
+ * byte), so a u8 HWC image needs two tables of [3][256] entries (built on the
+ * host, qconvnet/quant.py normalize_table / quantize_table; device memory
+ * here): ntab, the normalised fp32 value of byte p in channel c, and qlut, its
+ * quantize_per_tensor(in_scale, in_zp).  Exact by construction.
+ *
+ * General fallback: u8 NHWC [n,h,w,3] -> fp32 NCHW [n,3,h,w],
+ * x = ntab[c][img].  Any h, w and any byte alignment of img. */
+int qcn_u8img_normalize_f32_nchw(const uint8_t* img, int n, int h, int w, const float* ntab,
+                                 float* x, void* stream);
+
+/* qcn_conv12_fused_f32_nchw on raw images: img u8 NHWC [nimg,32,32,3] (4-byte
+ * aligned, QCN_ERR_ARG otherwise), the QuantStub by lookups in qlut while the
+ * window is staged.  The remaining arguments and the result are those of
+ * qcn_conv12_fused_f32_nchw fed with ntab[c][img]. */
+int qcn_conv12_fused_u8_nhwc(const uint8_t* img, int nimg, const uint8_t* qlut, int in_zp,
+                             const int8_t* w1_packed, const float* u1, const float* v1,
+                             const float* mult1, const int32_t* corr1, int z1, int relu1,
+                             const qcn_qdq_t* qdq1, int x2_zp, const int8_t* w2_packed,
+                             const float* u2, const float* v2, const float* mult2,
+                             const int32_t* corr2, int y_zp, int relu2, const qcn_qdq_t* qdq2,
+                             uint8_t* y, void* stream);
+
+/* qcn_convnet_convs_f32_nchw on raw images (img, qlut as above; in_zp ==
+ * layers[0].x_zp): the same forms by batch, the same planning
+ * (qcn_convnet_convs_form answers for both input kinds) and the same bytes in
+ * a2, a4 and a6. */
+int qcn_convnet_convs_u8_nhwc(const uint8_t* img, int nimg, const uint8_t* qlut, int in_zp,
+                              const qcn_conv_layer_t* layers, uint8_t* a2, uint8_t* a4, uint8_t* a6,
+                              int kmajor, void* stream);
+
 /* Two convolutions of one SimpleConvNet block in one launch: conv A
  * (cin -> cmid, no pool) then conv B (cmid -> cout, fused 2x2 max-pool).  A's
  * output never leaves LDS; the results are those of two qcn_conv3x3_u8s8_nhwc
