@@ -6,8 +6,8 @@
 // normalize_table) and this kernel only looks values up, so the result equals
 // the host transform bit for bit.  It feeds every path without a u8 input
 // stage of its own (the stand-alone conv1, GPU calibration, the fp32 and
-// dynamic models, the ResNet executors); the conv1+conv2 phase reads the bytes
-// itself (conv3x3_u8.hip).
+// dynamic models); the conv1+conv2 phase (conv3x3_u8.hip) and the ResNet stems
+// (resnet_stem.hip, stem_pack_u8_kernel below) read the bytes themselves.
 //
 // Memory-bound: 3 B in, 12 B out per pixel.  Persistent grid sized from the CU
 // count.  Quad form (h*w a multiple of 4, x 16-B aligned): a lane owns four
@@ -96,7 +96,55 @@ __global__ __launch_bounds__(kNormThreads) void u8img_normalize_pixel_kernel(
   }
 }
 
+// stem_pack_kernel (convgen.hip) on raw images: the QuantStub + row im2col of
+// the 7x7/2 pad-3 stem, out[n][iy][ox][32] byte 3*s + ch =
+// qlut[ch][img[n][iy][2*ox - 3 + s][ch]], the zero point outside the image and
+// in bytes 21..31.  The 7 columns of an entry are 21 contiguous image bytes
+// (byte loads: any w and any alignment of img); the u8 table sits in LDS.
+__global__ __launch_bounds__(kNormThreads) void stem_pack_u8_kernel(
+    const uint8_t* __restrict__ img, int n, int h, int w, int ow, const uint8_t* __restrict__ qlut,
+    int zp, uint8_t* __restrict__ y) {
+  __shared__ uint8_t tab[3 * 256];
+  for (int i = threadIdx.x; i < 3 * 256; i += kNormThreads) tab[i] = qlut[i];
+  __syncthreads();
+  const long long e = (long long)blockIdx.x * kNormThreads + threadIdx.x;
+  if (e >= (long long)n * h * ow) return;
+  const int ox = (int)(e % ow);
+  const long long row = e / ow;   // n * h + iy
+  uint32_t wd[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) wd[i] = splat_u8(zp);
+#pragma unroll
+  for (int s = 0; s < 7; ++s) {
+    const int ix = 2 * ox - 3 + s;
+    if (ix < 0 || ix >= w) continue;
+    const uint8_t* px = img + (row * w + ix) * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const uint32_t q = tab[ch * 256 + px[ch]];
+      const int b = 3 * s + ch;
+      wd[b >> 2] = (wd[b >> 2] & ~(0xffu << (8 * (b & 3)))) | (q << (8 * (b & 3)));
+    }
+  }
+  uint4* o = reinterpret_cast<uint4*>(y + e * 32);
+  o[0] = make_uint4(wd[0], wd[1], wd[2], wd[3]);
+  o[1] = make_uint4(wd[4], wd[5], wd[6], wd[7]);
+}
+
 }  // namespace qcn
+
+extern "C" int qcn_stem_pack_u8_nhwc(const uint8_t* img, int nimg, int h, int w, const uint8_t* qlut,
+                                     int zp, uint8_t* y, void* stream) {
+  if (!img || !qlut || !y || nimg <= 0 || h <= 0 || w <= 0 || zp < 0 || zp > 255) return QCN_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(y) & 15) return QCN_ERR_ARG;   // 16-byte stores
+  const int ow = (w - 1) / 2 + 1;
+  const long long total = (long long)nimg * h * ow;
+  const long long grid = (total + qcn::kNormThreads - 1) / qcn::kNormThreads;
+  if (grid > 0x7fffffffLL) return QCN_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(qcn::stem_pack_u8_kernel, dim3((unsigned)grid), dim3(qcn::kNormThreads), 0,
+                     (hipStream_t)stream, img, nimg, h, w, ow, qlut, zp, y);
+  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+}
 
 extern "C" int qcn_u8img_normalize_f32_nchw(const uint8_t* img, int n, int h, int w, const float* ntab,
                                             float* x, void* stream) {

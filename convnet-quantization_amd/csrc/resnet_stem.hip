@@ -27,6 +27,14 @@
 //   D  the 3x3/2 max-pool over CS (padding taps skipped; max commutes with the
 //      monotone requant, as qcn_maxpool3x3s2_u8_nhwc), 16-byte NHWC stores.
 // The next band's fp32 input is loaded into registers during C and D.
+//
+// Raw image input (U8 = true, qcn_resnet_stem_fused_u8_nhwc): the input is the
+// u8 NHWC image itself.  A QIN row is '3 bytes per column, channel fastest' —
+// the layout of an image row — and ToTensor -> Normalize -> QuantStub is a
+// function of (channel, byte), so phase A is a byte-wise lookup of the row in
+// the host's 3 x 256 table (quant.py quantize_table; a copy sits in LDS behind
+// the epilogue constants) and the prefetch carries 3 raw dwords per item in
+// place of 12 floats.  Phases B, C and D are the same code.
 #include "common.hpp"
 #include "qconvnet_abi.hpp"
 
@@ -68,12 +76,14 @@ struct StemCfg {
   static constexpr int R2_B = QIN_B > CS_B ? QIN_B : CS_B;
   static constexpr int OFF_EPI = OFF_R2 + R2_B;   // u | v | mult (fp32) | corr (int32), x 64 each
   static constexpr int LDS = OFF_EPI + 4 * C * 4;
+  static constexpr int OFF_LUT = LDS;             // u8 input only: the QuantStub table [3][256]
+  static constexpr int LDS_U8 = OFF_LUT + 3 * 256;
   static constexpr int NTH = 512;
   static constexpr int ITEMS = IR * (S / 4);      // phase A items: (row, 4 columns)
   static constexpr int NPF = (ITEMS + NTH - 1) / NTH;
   static_assert(PW % P == 0, "bands tile the pool rows");
   static_assert(S % 4 == 0, "4-column quantize items");
-  static_assert(LDS <= 160 * 1024, "fits one CU's LDS");
+  static_assert(LDS_U8 <= 160 * 1024, "fits one CU's LDS");
 };
 
 struct StemArgs {
@@ -86,9 +96,17 @@ struct StemArgs {
   const int* corr;
   int zp_y, lo;
   uint8_t* y;
+  // raw image input (x unused): u8 NHWC [n][S][S][3], 4-byte aligned, and the table
+  const uint8_t* img;
+  const uint8_t* qlut;
 };
 
-template <int S, int P = 2>
+// one phase-A item in flight: 4 columns x 3 channels, as fp32 planes or raw bytes
+struct StemRaw { uint32_t d[3]; };
+template <bool U8> struct StemPf { typedef float4 T[3]; };
+template <> struct StemPf<true> { typedef StemRaw T; };
+
+template <int S, int P = 2, bool U8 = false>
 __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
   using C = StemCfg<S, P>;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -98,6 +116,7 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
   uint8_t* tap = lds + C::OFF_TAP;
   uint8_t* r2 = lds + C::OFF_R2;
   float* epi = reinterpret_cast<float*>(lds + C::OFF_EPI);
+  const uint8_t* lut = lds + C::OFF_LUT;
   const uint32_t zp4 = splat_u8(a.zp);
 
   // epilogue constants and corr in LDS: a global load inside the band loop
@@ -107,6 +126,11 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
     epi[tid] = src[tid % C::C];
   } else if (tid < 4 * C::C) {
     reinterpret_cast<int*>(epi)[tid] = a.corr[tid - 3 * C::C];
+  }
+  if constexpr (U8) {   // the table is read in the first phase A
+    if (tid < 3 * 256 / 4)
+      reinterpret_cast<uint32_t*>(lds + C::OFF_LUT)[tid] = reinterpret_cast<const uint32_t*>(a.qlut)[tid];
+    __syncthreads();
   }
   // A blocks (couts 32 i .. 32 i + 31) of all 7 tap-row chunks, in registers
   v4i wa[2][7];
@@ -123,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
   const int bbeg = (int)((long)blockIdx.x * nb / gridDim.x);
   const int bend = (int)((long)(blockIdx.x + 1) * nb / gridDim.x);
   // phase-A prefetch: item it = tid + NTH k -> (QIN row, 4-column group)
-  float4 pf[C::NPF][3];
+  typename StemPf<U8>::T pf[C::NPF];
   auto prefetch = [&](int band) {
     const int img = band / C::BANDS, pr0 = (band % C::BANDS) * C::P;
 #pragma unroll
@@ -132,10 +156,16 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
       const int row = it / (S / 4), c4 = it % (S / 4);
       const int iy = 4 * pr0 - 5 + row;
       const bool ok = band < bend && it < C::ITEMS && iy >= 0 && iy < S;
+      if constexpr (U8) {
+        // 12 bytes at a multiple of 12 from a 4-byte aligned base
+        pf[k] = ok ? *reinterpret_cast<const StemRaw*>(a.img + (((long)img * S + iy) * S + 4 * c4) * 3)
+                   : StemRaw{{0u, 0u, 0u}};
+      } else {
 #pragma unroll
-      for (int c = 0; c < 3; ++c)
-        pf[k][c] = ok ? *reinterpret_cast<const float4*>(a.x + (((long)img * 3 + c) * S + iy) * S + 4 * c4)
-                      : make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int c = 0; c < 3; ++c)
+          pf[k][c] = ok ? *reinterpret_cast<const float4*>(a.x + (((long)img * 3 + c) * S + iy) * S + 4 * c4)
+                        : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
     }
   };
   auto quant = [&](float v) {
@@ -156,7 +186,21 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
         const int row = it / (S / 4), c4 = it % (S / 4);
         const int iy = 4 * pr0 - 5 + row;
         uint32_t d[3];
-        if (iy >= 0 && iy < S) {
+        if constexpr (U8) {
+          if (iy >= 0 && iy < S) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+              const uint32_t w = pf[k].d[j];
+              uint32_t o = 0;
+#pragma unroll
+              for (int e = 0; e < 4; ++e)   // byte 4 j + e of the 12: channel (4 j + e) % 3
+                o |= (uint32_t)lut[((4 * j + e) % 3) * 256 + ((w >> (8 * e)) & 0xffu)] << (8 * e);
+              d[j] = o;
+            }
+          } else {
+            d[0] = d[1] = d[2] = zp4;
+          }
+        } else if (iy >= 0 && iy < S) {
           const float* f0 = &pf[k][0].x;
           const float* f1 = &pf[k][1].x;
           const float* f2 = &pf[k][2].x;
@@ -281,16 +325,17 @@ __global__ __launch_bounds__(512, 1) void stem_fused_kernel(StemArgs a) {
 }  // namespace qcn
 
 namespace {
-template <int S, int P = 2>
+template <int S, int P = 2, bool U8 = false>
 int launch_stem(const qcn::StemArgs& a, hipStream_t st) {
   using C = qcn::StemCfg<S, P>;
+  constexpr int LDS = U8 ? C::LDS_U8 : C::LDS;
   static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)qcn::stem_fused_kernel<S, P>, C::LDS, attr_done)) return QCN_ERR_HIP;
+  if (!qcn_set_lds_once((const void*)qcn::stem_fused_kernel<S, P, U8>, LDS, attr_done)) return QCN_ERR_HIP;
   const int ncu = qcn_cu_count();
   if (ncu <= 0) return QCN_ERR_HIP;
   const long nb = (long)a.n * C::BANDS;
   const int grid = (int)(nb < ncu ? nb : ncu);
-  hipLaunchKernelGGL((qcn::stem_fused_kernel<S, P>), dim3(grid), dim3(C::NTH), C::LDS, st, a);
+  hipLaunchKernelGGL((qcn::stem_fused_kernel<S, P, U8>), dim3(grid), dim3(C::NTH), LDS, st, a);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 }  // namespace
@@ -316,4 +361,24 @@ extern "C" int qcn_resnet_stem_fused(const float* x, int nimg, int h, int w, flo
   // 106.2-108.2 -> 108.3-109.0 K img/s same box (1 pool row, two workgroups
   // per CU at 128 VGPRs: 0.549 ms; profiles/r03_diag_resnet_stem_band_ab.txt)
   return launch_stem<224, 4>(a, st);
+}
+
+extern "C" int qcn_resnet_stem_fused_u8_nhwc(const uint8_t* img, int nimg, int h, int w,
+                                             const uint8_t* qlut, int in_zp, const int8_t* w_packed,
+                                             int cout, const float* u, const float* v,
+                                             const float* mult, const int32_t* corr, int y_zp,
+                                             int relu, uint8_t* y, void* stream) {
+  if (!img || !qlut || !w_packed || !u || !v || !mult || !corr || !y) return QCN_ERR_ARG;
+  if (nimg <= 0 || h <= 0 || w <= 0 || in_zp < 0 || in_zp > 255 || y_zp < 0 || y_zp > 255)
+    return QCN_ERR_ARG;
+  if (h != w || (h != 224 && h != 64) || cout != 64) return QCN_ERR_UNSUPPORTED;
+  if ((long)nimg * 3 * h * w >= (1L << 31)) return QCN_ERR_UNSUPPORTED;
+  // the image rows and the table are dword loads
+  if ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(qlut)) & 3) return QCN_ERR_ARG;
+  qcn::StemArgs a{};
+  a.img = img; a.qlut = qlut; a.n = nimg; a.zp = in_zp; a.w = w_packed;
+  a.u = u; a.v = v; a.mult = mult; a.corr = corr; a.zp_y = y_zp; a.lo = relu ? y_zp : 0; a.y = y;
+  hipStream_t st = (hipStream_t)stream;
+  if (h == 64) return launch_stem<64, 2, true>(a, st);
+  return launch_stem<224, 4, true>(a, st);   // band shape as for the fp32 input
 }

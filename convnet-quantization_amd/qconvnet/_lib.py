@@ -70,6 +70,9 @@ SIGNATURES = {
                                        C.POINTER(QDQ), i32, vp, vp, vp, vp, vp, i32, i32,
                                        C.POINTER(QDQ), vp, vp]),
     "qcn_convnet_convs_u8_nhwc": (i32, [vp, i32, vp, i32, C.POINTER(ConvLayer), vp, vp, vp, i32, vp]),
+    "qcn_resnet_stem_fused_u8_nhwc": (i32, [vp, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, i32,
+                                            i32, vp, vp]),
+    "qcn_stem_pack_u8_nhwc": (i32, [vp, i32, i32, i32, vp, i32, vp, vp]),
     "qcn_linear_u8s8": (i32, [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, f32, vp]),
     "qcn_classifier_workspace_size": (i64, [i32, i32]),
     "qcn_pack_fc_kmajor": (i32, [vp, i32, i32, vp]),

@@ -249,16 +249,16 @@ def conv12_fused(x, in_scale, in_zp, l1, l2, out=None):
 
 
 # ------------------------------------------------------ raw u8 image input
-def _u8_images(x, name, hw=None):
+def _u8_images(x, name, hw=None, align=None):
     """A device u8 NHWC batch the kernels can read: checked for layout, made
-    contiguous, and moved to a 4-byte boundary when ``hw`` (the conv entries'
-    fixed size) is given."""
+    contiguous, and moved to a 4-byte boundary when ``align`` (by default:
+    when ``hw``, the conv entries' fixed size, is given)."""
     from .quant import check_u8_images
     if not x.is_cuda:
         raise ValueError(f"{name}: expected a device tensor")
     check_u8_images(x, hw)
     x = x.contiguous()
-    if hw is not None and x.data_ptr() % 4:
+    if (hw is not None if align is None else align) and x.data_ptr() % 4:
         x = x.clone()
     return x
 
@@ -690,6 +690,41 @@ def stem_fused(x, scale, zp, layer, out=None):
     check(lib().qcn_resnet_stem_fused(_ptr(x), n, h, w, float(scale), int(zp), _ptr(d.w), d.cout,
                                       _ptr(d.u), _ptr(d.v), _ptr(d.mult), _ptr(d.corr), int(d.z_y),
                                       int(bool(d.relu)), _ptr(out), _stream()), "stem_fused")
+    return out
+
+
+def stem_pack_u8(img, qlut, zp, out=None):
+    """stem_pack() on raw images (qcn_stem_pack_u8_nhwc): ``img`` u8 NHWC
+    [n,h,w,3] of any size and byte alignment, ``qlut`` the device uint8 [3,256]
+    QuantStub table (quant.quantize_table).  The result equals stem_pack() of
+    the table-expanded input bit for bit."""
+    img = _u8_images(img, "stem_pack_u8.img")
+    _need_qlut(qlut, "stem_pack_u8.qlut")
+    n, h, w, _ = img.shape
+    if out is None:
+        out = torch.empty((n, h, (w - 1) // 2 + 1, 32), dtype=torch.uint8, device=img.device)
+    check(lib().qcn_stem_pack_u8_nhwc(_ptr(img), n, h, w, _ptr(qlut), int(zp), _ptr(out), _stream()),
+          "stem_pack_u8")
+    return out
+
+
+def stem_fused_u8(img, qlut, zp, layer, out=None):
+    """stem_fused() on raw images (qcn_resnet_stem_fused_u8_nhwc): ``img`` u8
+    NHWC [n,s,s,3], s in {224, 64} (a batch off a 4-byte boundary is moved to
+    one first), ``qlut`` as for stem_pack_u8.  The result equals stem_fused()
+    of the table-expanded input bit for bit."""
+    img = _u8_images(img, "stem_fused_u8.img", align=True)
+    _need_qlut(qlut, "stem_fused_u8.qlut")
+    n, h, w, _ = img.shape
+    d = layer
+    if h != w or d.cout != 64:
+        raise ValueError("stem_fused_u8: square input, 64 output channels")
+    if out is None:
+        out = torch.empty((n, h // 4, w // 4, 64), dtype=torch.uint8, device=img.device)
+    check(lib().qcn_resnet_stem_fused_u8_nhwc(_ptr(img), n, h, w, _ptr(qlut), int(zp), _ptr(d.w), d.cout,
+                                              _ptr(d.u), _ptr(d.v), _ptr(d.mult), _ptr(d.corr),
+                                              int(d.z_y), int(bool(d.relu)), _ptr(out), _stream()),
+          "stem_fused_u8")
     return out
 
 

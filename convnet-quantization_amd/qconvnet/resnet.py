@@ -14,7 +14,8 @@ in fp32, ReLU'd and quantized with the block output's qparams.
 Device pipeline per forward (all u8 NHWC, every launch a hand-written HIP
 kernel on the current stream, capturable into a HIP graph):
   stem_pack (QuantStub + 7-tap row im2col) -> conv 7x1 (the 7x7/2 stem) ->
-  maxpool 3x3/2 -> 16 x [conv1x1+ReLU -> conv3x3(/2)+ReLU -> conv1x1
+  maxpool 3x3/2 (one launch, stem_fused, at 224x224 and 64x64; both forms
+  read fp32 NCHW or the raw uint8 NHWC images) -> 16 x [conv1x1+ReLU -> conv3x3(/2)+ReLU -> conv1x1
   (-> downsample conv1x1(/2)) -> add+ReLU] -> avgpool (u8, qparams kept) -> fc (fp32 logits)
 """
 from __future__ import annotations
@@ -169,8 +170,9 @@ def quantize_resnet(model, calib_batches, device="cuda", per_channel=True, calib
 class QuantizedResNet:
     """Duck-typed int8 ResNet (eval / cpu / to / __call__ like the reference's
     models.*): fp32 [N,3,H,W] in, fp32 [N,num_classes] logits out.  Raw uint8
-    NHWC images [N,H,W,3] are normalised with ``mean`` / ``std`` on the device
-    first (ops.normalize_u8; the stem itself reads fp32)."""
+    NHWC images [N,H,W,3] go to the stem as they are: ToTensor -> Normalize
+    (``mean`` / ``std``) -> QuantStub is the 3 x 256 byte table ``qlut`` the
+    stem kernels look the image bytes up in."""
 
     def __init__(self, spec, device="cuda", mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.spec = spec
@@ -223,6 +225,8 @@ class QuantizedResNet:
     def _upload(self):
         sp = self.spec
         self.in_scale, self.in_zp = sp["in"]
+        # ToTensor -> Normalize -> QuantStub per (channel, byte)
+        self.qlut = Q.quantize_table(self.ntab.cpu(), self.in_scale, self.in_zp).to(self.device)
         self.stem = self._layer(sp["stem"], stem=True)
         self.blocks = []
         for e in sp["blocks"]:
@@ -241,12 +245,24 @@ class QuantizedResNet:
 
     def _stem_fusable(self, x):
         """The one-launch stem (qcn_resnet_stem_fused) covers torchvision's
-        7x7/2 pad-3 64-channel stem at 224x224 and 64x64 inputs."""
+        7x7/2 pad-3 64-channel stem at 224x224 and 64x64 inputs (fp32 NCHW or
+        u8 NHWC)."""
         e = self.spec["stem"]
+        c, h, w = (x.shape[3], x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else x.shape[1:]
         return (self.stem.cout == 64
                 and tuple(np.asarray(e["w"]).shape[1:]) == (3, 7, 7)
                 and tuple(e["stride"]) == (2, 2) and tuple(e["pad"]) == (3, 3)
-                and x.shape[1] == 3 and x.shape[2] == x.shape[3] and x.shape[2] in (224, 64))
+                and c == 3 and h == w and h in (224, 64))
+
+    def _input(self, x):
+        """What the stem launches read, on the model's device: fp32 NCHW, or a
+        raw u8 NHWC batch as it is — contiguous and on a 4-byte boundary (the
+        fused stem loads its rows as dwords)."""
+        if x.dtype != torch.uint8:
+            return x.to(self.device, torch.float32)
+        Q.check_u8_images(x)
+        x = x.to(self.device).contiguous()
+        return x.clone() if x.data_ptr() % 4 else x
 
     @staticmethod
     def _join_reduce_fusable(c3, c1n):
@@ -270,7 +286,7 @@ class QuantizedResNet:
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
-            return self._run(normalized_input(x, self.device, self.ntab), keep, marks)
+            return self._run(self._input(x), keep, marks)
 
     def _run(self, x, keep, marks):
         g = self._steps(x, keep, marks)
@@ -289,14 +305,18 @@ class QuantizedResNet:
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
-            x = normalized_input(x, self.device, self.ntab)
+            x = self._input(x)
             main = torch.cuda.current_stream(self.device)
             if len(getattr(self, "_side", ())) < nsplit:
                 self._side = [torch.cuda.Stream(device=self.device) for _ in range(nsplit)]
             streams = self._side[:nsplit]
             for s in streams:
                 s.wait_stream(main)
-            gens = [self._steps(c, False, None) for c in x.chunk(nsplit)]
+            chunks = x.chunk(nsplit)
+            # (u8: H * W * 3 bytes per image is a multiple of 4 at both fused sizes)
+            assert not (x.dtype == torch.uint8 and self._stem_fusable(x)) or all(
+                c.data_ptr() % 4 == 0 for c in chunks), "u8 slices off the 4-byte boundary"
+            gens = [self._steps(c, False, None) for c in chunks]
             outs = [None] * len(gens)
             live = list(range(len(gens)))
             while live:
@@ -325,12 +345,19 @@ class QuantizedResNet:
 
         sp = self.spec
         mark("start")
+        u8 = x.dtype == torch.uint8   # raw images: the QuantStub is a lookup in qlut
         if self._stem_fusable(x):   # quantize + conv + ReLU + max-pool in one launch
-            q = ops.stem_fused(x, self.in_scale, self.in_zp, self.stem)
+            if u8:
+                q = ops.stem_fused_u8(x, self.qlut, self.in_zp, self.stem)
+            else:
+                q = ops.stem_fused(x, self.in_scale, self.in_zp, self.stem)
             mark("conv")   # carries the stem MACs (bench / resnet_layers accounting)
             yield
         else:
-            q = ops.stem_pack(x, self.in_scale, self.in_zp)
+            if u8:
+                q = ops.stem_pack_u8(x, self.qlut, self.in_zp)
+            else:
+                q = ops.stem_pack(x, self.in_scale, self.in_zp)
             mark("stem_pack")
             yield
             q = ops.conv(q, self.in_zp, self.stem)
@@ -410,8 +437,8 @@ class QuantizedResNet:
     @torch.no_grad()
     def forward(self, x):
         host = not x.is_cuda
-        # (raw uint8 images: the bytes are moved, then normalised on the device)
-        xd = normalized_input(x, self.device, self.ntab).contiguous()
+        # (raw uint8 images: the bytes are moved and read by the stem as they are)
+        xd = self._input(x).contiguous()
         # two interleaved stream slices fill each layer's last workgroup round
         # (+6 % at batch 512, profiles/r02_diag_resnet_streams.txt)
         out = self.run_streams(xd, 2) if xd.shape[0] >= 128 else self.run(xd).clone()

@@ -150,8 +150,9 @@ def quantize_resnet_reference(model, calib_batches, device="cuda", per_channel=T
 class QuantizedResNetQDQ:
     """Duck-typed live-stub int8 ResNet (eval / cpu / to / __call__): fp32
     [N,3,H,W] in, fp32 [N,num_classes] logits out.  Raw uint8 NHWC images
-    [N,H,W,3] are normalised with ``mean`` / ``std`` on the device first
-    (ops.normalize_u8)."""
+    [N,H,W,3] go to the stem's row pack as they are: ToTensor -> Normalize
+    (``mean`` / ``std``) -> the stem's QuantStub is the 3 x 256 byte table
+    ``qlut``."""
 
     def __init__(self, spec, device="cuda", mean=IMAGENET_MEAN, std=IMAGENET_STD):
         self.spec = spec
@@ -185,6 +186,8 @@ class QuantizedResNetQDQ:
     def _upload(self):
         sp = self.spec
         self.stem = self._layer(sp["stem"], stem=True)
+        # ToTensor -> Normalize -> the stem's QuantStub per (channel, byte)
+        self.qlut = Q.quantize_table(self.ntab.cpu(), self.stem.s_x, self.stem.z_x).to(self.device)
         self.blocks = []
         for e in sp["blocks"]:
             b = {k: (self._layer(e[k]) if e.get(k) is not None else None) for k in ("c1", "c2", "c3", "ds")}
@@ -203,17 +206,29 @@ class QuantizedResNetQDQ:
         self.fc = d
         self.num_classes = w.shape[0]
 
+    def _input(self, x):
+        """What the stem pack reads, on the model's device: fp32 NCHW, or a raw
+        u8 NHWC batch as it is (contiguous; any byte alignment)."""
+        if x.dtype != torch.uint8:
+            return x.to(self.device, torch.float32)
+        Q.check_u8_images(x)
+        return x.to(self.device).contiguous()
+
     def run(self, x, keep=False):
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
-            return self._run(normalized_input(x, self.device, self.ntab), keep)
+            return self._run(self._input(x), keep)
 
     def _run(self, x, keep):
         inter = {}
         st = self.stem
         first = self.blocks[0]["c1"] if self.blocks else None
-        y = ops.conv(ops.stem_pack(x, st.s_x, st.z_x), st.z_x, st)
+        if x.dtype == torch.uint8:   # raw images: the QuantStub is a lookup in qlut
+            rows = ops.stem_pack_u8(x, self.qlut, st.z_x)
+        else:
+            rows = ops.stem_pack(x, st.s_x, st.z_x)
+        y = ops.conv(rows, st.z_x, st)
         xf, xq = ops.dq_bn_relu_maxpool(y, st.s_y, st.z_y, st.alpha, st.beta,
                                         first.s_x if first else None, first.z_x if first else 0)
         if keep:
@@ -248,7 +263,7 @@ class QuantizedResNetQDQ:
     @torch.no_grad()
     def forward(self, x):
         host = not x.is_cuda
-        xd = normalized_input(x, self.device, self.ntab).contiguous()
+        xd = self._input(x).contiguous()
         out = self.run(xd).clone()
         if host or self.host_io:
             return out.cpu()

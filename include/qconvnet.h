@@ -231,6 +231,28 @@ int qcn_convnet_convs_u8_nhwc(const uint8_t* img, int nimg, const uint8_t* qlut,
                               const qcn_conv_layer_t* layers, uint8_t* a2, uint8_t* a4, uint8_t* a6,
                               int kmajor, void* stream);
 
+/* qcn_resnet_stem_fused on raw images: img u8 NHWC [nimg,h,w,3] and qlut (both
+ * 4-byte aligned, QCN_ERR_ARG otherwise); the QuantStub is a byte-wise lookup
+ * of each image row while the band is staged, so the data loader's ToTensor ->
+ * Normalize (dataset_manager.py:41-44) and the QuantStub ahead of conv1
+ * (custom_quantization_model.py:127) cost no launch and no fp32 copy of the
+ * batch; replaces qcn_u8img_normalize_f32_nchw + qcn_resnet_stem_fused.
+ * The remaining arguments, the envelope (h == w in {224, 64}, cout == 64, else
+ * QCN_ERR_UNSUPPORTED) and the result are those of qcn_resnet_stem_fused fed
+ * with ntab[c][img]. */
+int qcn_resnet_stem_fused_u8_nhwc(const uint8_t* img, int nimg, int h, int w, const uint8_t* qlut,
+                                  int in_zp, const int8_t* w_packed, int cout, const float* u,
+                                  const float* v, const float* mult, const int32_t* corr,
+                                  int y_zp, int relu, uint8_t* y, void* stream);
+
+/* qcn_stem_pack_f32_nchw on raw images (the general stem fallback): QuantStub
+ * + row im2col, y[n][h][ow][32] byte 3*s+ch = qlut[ch][img[n][iy][2*ox-3+s][ch]],
+ * zp outside the image and in bytes 21..31; ow = (w-1)/2 + 1.  Any h, w and
+ * any byte alignment of img; y 16-byte aligned.  The bytes are those of
+ * qcn_stem_pack_f32_nchw fed with ntab[c][img]. */
+int qcn_stem_pack_u8_nhwc(const uint8_t* img, int nimg, int h, int w, const uint8_t* qlut, int zp,
+                          uint8_t* y, void* stream);
+
 /* Two convolutions of one SimpleConvNet block in one launch: conv A
  * (cin -> cmid, no pool) then conv B (cmid -> cout, fused 2x2 max-pool).  A's
  * output never leaves LDS; the results are those of two qcn_conv3x3_u8s8_nhwc
