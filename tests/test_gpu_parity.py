@@ -113,7 +113,11 @@ def test_conv_golden(dev, golden_dir):
     (3, 4, 256, 256, True, 0), (1, 6, 64, 64, False, 9), (2, 8, 192, 64, True, 1)])
 def test_conv_tuned_vs_oracle(dev, n, h, cin, cout, pool, zx):
     """Every tuned instantiation (and the generic fallback) against the oracle,
-    full-range u8 inputs, partial workgroups (odd image counts)."""
+    full-range u8 inputs and weights, partial workgroups (odd image counts).
+    The OUTPUTS are not full-range: s_y in 0.5..3 against s_x s_w = 6e-5 puts
+    them at roughly z_y .. z_y + 40, so the upper clamp is never reached;
+    test_conv_tuned_full_range_vs_oracle covers outputs that span
+    [lower clamp, 255] and saturate at both ends."""
     from qconvnet import ops, quant as Q
     rng = np.random.default_rng(n * 1000 + h * 10 + cin + cout)
     qx = rng.integers(0, 256, (n, h, h, cin)).astype(np.uint8)
@@ -132,6 +136,59 @@ def test_conv_tuned_vs_oracle(dev, n, h, cin, cout, pool, zx):
 def _pool_acc(acc):
     n, h, w, c = acc.shape
     return acc.reshape(n, h // 2, 2, w // 2, 2, c).max(axis=(2, 4))
+
+
+@pytest.mark.parametrize("epilogue", ["fast", "general", "declined"])
+@pytest.mark.parametrize("n,h,cin,cout,pool,zx", [
+    (3, 32, 64, 64, True, 0), (2, 32, 64, 64, False, 7), (3, 16, 64, 128, False, 0),
+    (2, 16, 128, 128, True, 3), (5, 8, 128, 256, False, 0), (5, 8, 256, 256, True, 250),
+    (3, 4, 256, 256, True, 0), (1, 6, 64, 64, False, 9), (2, 8, 192, 64, True, 1),
+    (1, 56, 64, 64, False, 5), (1, 28, 128, 128, False, 0)])
+def test_conv_tuned_full_range_vs_oracle(dev, n, h, cin, cout, pool, zx, epilogue):
+    """The per-layer kernel (the reference of every "equals layerwise" test)
+    with outputs over the whole u8 range: the shapes of
+    test_conv_tuned_vs_oracle and the two ResNet instantiations, full-range
+    inputs and weights, s_y / z_y derived from the accumulators
+    (convchain.layer_entry) so the requant output saturates at both ends, in
+    three epilogues: fast (z_y = 0, ReLU: v_cvt_pk_u8_f32 saturates alone),
+    general (z_y != 0, no ReLU: the med3 clamps), and a declined QDQ hand-off
+    (qdq_next_f after the requant, exact .5 ties).  The coverage condition is
+    asserted on the reference before the comparison."""
+    import convchain as CC
+    from qconvnet import _lib, ops
+    rng = np.random.default_rng([n, h, cin, cout, zx, ("fast", "general", "declined").index(epilogue)])
+    qx = rng.integers(0, 256, (n, h, h, cin)).astype(np.uint8)
+
+    def acc_of(w):
+        acc = qref.conv_acc_nhwc(qx, zx, w, (1, 1), (1, 1))
+        return _pool_acc(acc) if pool else acc
+
+    declined = epilogue == "declined"
+    e, acc = CC.layer_entry(rng, acc_of, (cout, cin, 3, 3), F32(0.02), zx, "F" if epilogue == "fast" else "G",
+                            epilogue == "fast", False, declined)
+    qdq = None
+    if declined:
+        e["next"] = (F32(2.0) * e["s_y"], 5)
+        assert CC.entry_found(_lib.load(), e) is False
+        qdq = ops.qdq_struct(e["s_y"], e["z_y"], *e["next"])
+    u, v, mult = qref.requant_constants(e["s_x"], e["s_w"], e["s_y"], e["b"])
+    ref = qref.requantize(acc, u, v, mult, e["z_y"], e["relu"])
+    lo = CC.conv_lo(e)
+    at_lo, at_hi, levels = np.mean(ref == lo), np.mean(ref == 255), np.unique(ref).size / (256 - lo)
+    print(f"z_y {e['z_y']} lo {lo} at_lo {at_lo:.3f} at_255 {at_hi:.3f} levels {levels:.3f}")
+    assert (epilogue == "fast") == (e["z_y"] == 0)
+    assert at_lo >= 0.02 and at_hi >= 0.02 and levels >= 0.90, (at_lo, at_hi, levels)
+    if declined:
+        ref = CC.handoff(ref, e)
+        assert np.unique(ref).size >= 64
+    c = dict(qx=qx, zx=np.int64(zx), s_x=e["s_x"], w=np.ascontiguousarray(e["w"].transpose(0, 2, 3, 1)),
+             s_w=np.asarray(e["s_w"]), b=e["b"], s_y=e["s_y"], zy=np.int64(e["z_y"]),
+             relu=np.int64(e["relu"]))
+    got = _run_conv(dev, c, pool=pool, qdq=qdq)
+    assert got.shape == ref.shape
+    bad = np.argwhere(got != ref)
+    assert bad.size == 0, (f"{len(bad)} of {ref.size} differ; first at (image, y, x, channel) "
+                           f"{tuple(bad[0])}: got {got[tuple(bad[0])]} want {ref[tuple(bad[0])]}")
 
 
 def test_conv_qdq_handoff(dev):
