@@ -2,19 +2,21 @@
 // QuantizedLinearReLU fc1 -> QuantizedLinear fc2 -> DeQuantStub), in two
 // launches instead of two full GEMM kernels:
 //
-//  1. fc_splitk_kernel: fc1's u8 x s8 GEMM (M = batch, K = 4096, N = 512) split
-//     four ways along K.  From 1024 rows up a workgroup owns a 128 (rows) x 64
-//     (features) tile of one K quarter and its four waves each compute 64 x 32
-//     (fc_splitk_kernel<64>); below 1024 rows workgroups own 64 x 64 tiles and
-//     each wave 32 x 32 (fc_splitk_kernel<32>: twice the workgroups, so a
-//     small batch still fills the CUs).  Both on v_mfma_i32_32x32x32_i8
+//  1. fc_splitk_kernel*: fc1's u8 x s8 GEMM (M = batch, K = 4096, N = 512)
+//     split along K.  From 1024 rows up a workgroup owns a 64 (rows) x 64
+//     (features) tile of one K half, each of its four waves accumulates the
+//     whole tile over a quarter of that half, and the waves' sums meet in LDS
+//     (fc_splitk_kernel_wavek: no fragment is loaded twice in a workgroup,
+//     two partial planes).  Below 1024 rows K is split four ways over
+//     workgroups that own 64 x 64 tiles, each wave 32 x 32
+//     (fc_splitk_kernel<32>: twice the workgroups, so a small batch still
+//     fills the CUs).  Both on v_mfma_i32_32x32x32_i8
 //     straight from global memory.  Both operands are
 //     chunk-major ([K/32][rows][32]: conv6 writes its output that way, the
 //     weights are packed so at upload), so every fragment load is one
 //     contiguous 1 KB — row-major operands (4 KB row stride) ran 2-3x slower.
-//     Each XCD takes one K quarter and half of the output tiles, so its L2
-//     holds a quarter of W and half of X's quarter.  int32 partial sums go to a
-//     workspace (4 x M x 512 x 4 B = 8 MB at batch 1024).
+//     int32 partial sums go to a workspace (2 x M x 512 x 4 B = 4 MB at
+//     batch 1024; 4 x M x 512 x 4 B below 1024 rows).
 //  2. fc_finish_kernel: one wave per row sums the partials, adds the
 //     zero-point correction, requantizes fc1 (+ReLU), writes the u8 fc1 row,
 //     then computes fc2 (512 -> n2 <= 16) from the row it holds in registers
@@ -25,16 +27,17 @@
 
 namespace qcn {
 
-constexpr int FC_S = 4;      // K split
+constexpr int FC_S = 4;      // K split below 1024 rows (and the workspace's upper bound)
+constexpr int FC_S2 = 2;     // K split over workgroups from 1024 rows up
 constexpr int FC_N1 = 512;   // fc1 features handled by the finisher (64 lanes x 8)
 constexpr int FC_N2 = 16;    // max fc2 outputs
-// workspace: the split-K partials, [FC_S][m][n1] int32
+// workspace: the split-K partials, [S][m][n1] int32, S = FC_S2 or FC_S
 
 // X' [K/32][m][32], W' [K/32][n][32] (chunk-major: a 32-row MFMA fragment of
 // one 32-byte K chunk is one contiguous 1 KB, every wave-load fully coalesced).
-// RW: rows per wave — 64 (two MFMA row blocks, 128-row workgroups) or 32
-// (one block, 64-row workgroups: twice the workgroups at the same partial
-// traffic, for batches too small to fill the CUs with 128-row tiles).
+// RW: rows per wave — 32 (one MFMA row block, 64-row workgroups) is the form
+// in use, for batches below 1024 rows; 64 (two row blocks, 128-row
+// workgroups) was the large-batch form before fc_splitk_kernel_wavek.
 // fc1's split-K partial tile of workgroup blockIdx.x; returns its (row
 // block, feature block, K quarter)
 template <int RW>
@@ -126,16 +129,133 @@ __global__ __launch_bounds__(256) void fc_splitk_kernel(const uint8_t* __restric
   fc_splitk_tile<RW>(x, m, k, w, n, part);
 }
 
-// 64-row tiles below 1024 rows (batch 256: 128 workgroups instead of 64)
-inline void launch_fc_splitk(const uint8_t* x, int m, int k, const int8_t* w1, int n1, int* part,
-                             hipStream_t st) {
+// From 1024 rows up: workgroup = 64 rows x 64 features of one K half; wave w
+// accumulates the whole tile (2 x 2 MFMA blocks, 64 accumulator registers)
+// over the w-th quarter of that half, so each X and W fragment of the tile is
+// loaded by exactly one wave: (64 + 64) rows x k / 2 bytes per workgroup
+// through the CU's vector-memory path (256 KB at k = 4096) against 384 KB for
+// 128 x 64 tiles of a K quarter with 64 x 32 wave tiles.  X is the MFMA's A
+// operand here, so D is [row][feature] with the feature on the lane.
+// The four waves' sums meet in LDS: wave b finishes block b (row half b >> 1,
+// feature half b & 1) and parks the other three in fragment order (lane-linear
+// int4: conflict-free both ways), one barrier.  Each partial store writes 32
+// consecutive features of two rows: whole 128-byte lines.
+// NBAT: the wave's load batches when known at compile time (k = 1024 NBAT), else 0.
+template <int NBAT>
+__global__ __launch_bounds__(256, 2) void fc_splitk_kernel_wavek(const uint8_t* __restrict__ x, int m, int k,
+                                                              const int8_t* __restrict__ w, int n,
+                                                              int* __restrict__ part) {
+  __shared__ int4 red[4][3][4][64];   // [block][parking wave - block - 1 (mod 4)][register quad][lane]: 48 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // linear tile order (row block, feature block, K half).  A K-half-major
+  // order over the XCDs (XCD x: K half x % 2, a quarter of the tiles) fetches
+  // less beyond L2 and measured 0.1-0.2 us slower
+  // (profiles/r07_diag_fc_wavek_ab.txt)
+  const int NB = n / 64, t = blockIdx.x;
+  const int mb = t / (NB * FC_S2), rem = t % (NB * FC_S2), nb = rem / FC_S2, s = rem % FC_S2;
+  const int row0 = mb * 64, col0 = nb * 64;
+  const int kcs = (k / 32) / (FC_S2 * 4), kc0 = (s * 4 + wave) * kcs;   // this wave's K chunks
+  // fragment lane (l32, hi): row l32, bytes [16 hi, 16 hi + 16) of the chunk
+  const int frag = (lane & 31) * 32 + (lane >> 5) * 16;
+  const uint8_t* xa = x + ((long)kc0 * m + row0) * 32 + frag;
+  const int8_t* wa = w + ((long)kc0 * n + col0) * 32 + frag;
+  const long xs = (long)m * 32, ws = (long)n * 32;   // bytes per K chunk
+
+  v16i acc[4] = {(v16i){0}, (v16i){0}, (v16i){0}, (v16i){0}};   // block 2 * (row half) + feature half
+  constexpr int U = 4;   // K chunks per load batch; two batches in flight (kcs is a multiple of 4)
+  v4i fw[2][U][2];
+  uint4 fx[2][U][2];
+  auto load = [&](int buf, int c) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      fw[buf][u][0] = *reinterpret_cast<const v4i*>(wa + (c + u) * ws);
+      fw[buf][u][1] = *reinterpret_cast<const v4i*>(wa + (c + u) * ws + 1024);
+      fx[buf][u][0] = *reinterpret_cast<const uint4*>(xa + (c + u) * xs);
+      fx[buf][u][1] = *reinterpret_cast<const uint4*>(xa + (c + u) * xs + 1024);
+    }
+  };
+  auto mm = [&](int buf) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint4 a = fx[buf][u][0], b = fx[buf][u][1];
+      const v4i a0 = (v4i){(int)xor80(a.x), (int)xor80(a.y), (int)xor80(a.z), (int)xor80(a.w)};
+      const v4i a1 = (v4i){(int)xor80(b.x), (int)xor80(b.y), (int)xor80(b.z), (int)xor80(b.w)};
+      acc[0] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, fw[buf][u][0], acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, fw[buf][u][1], acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, fw[buf][u][0], acc[2], 0, 0, 0);
+      acc[3] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, fw[buf][u][1], acc[3], 0, 0, 0);
+    }
+  };
+  if constexpr (NBAT == 0) {
+    // a conditional load joins ahead of the MFMAs here, and at such a join
+    // the compiler waits for every outstanding load, the batch just issued
+    // included
+    load(0, 0);
+    for (int c = 0; c < kcs; c += 2 * U) {
+      if (c + U < kcs) load(1, c + U);
+      mm(0);
+      if (c + 2 * U < kcs) load(0, c + 2 * U);
+      if (c + U < kcs) mm(1);
+    }
+  } else {
+    // straight-line: each mm waits for its own batch only, two batches in
+    // flight.  The scheduling barriers keep every batch's loads together
+    // and ahead of the previous batch's MFMAs; left alone, the scheduler
+    // sinks each load to just before its use to save registers.
+    load(0, 0);
+#pragma unroll
+    for (int b = 0; b < NBAT; ++b) {
+      if (b + 1 < NBAT) load((b + 1) & 1, (b + 1) * U);
+      __builtin_amdgcn_sched_barrier(0);
+      mm(b & 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // park the three blocks other waves finish (b is a compile-time index: a
+  // run-time one would put acc in scratch)
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    if (b != wave) {
+      const int j = ((wave - b) & 3) - 1;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        red[b][j][g][lane] = make_int4(acc[b][4 * g], acc[b][4 * g + 1], acc[b][4 * g + 2], acc[b][4 * g + 3]);
+    }
+  }
+  __syncthreads();
+  // D[row][feature]: lane (l32 = feature, hi) holds rows 8g + 4hi + e
+  const int l32 = lane & 31, hi = lane >> 5;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    if (b == wave) {
+      int* pp = part + ((long)s * m + row0 + (b >> 1) * 32 + 4 * hi) * n + col0 + (b & 1) * 32 + l32;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int4 p0 = red[b][0][g][lane], p1 = red[b][1][g][lane], p2 = red[b][2][g][lane];
+        pp[(long)(8 * g) * n] = acc[b][4 * g] + p0.x + p1.x + p2.x;
+        pp[(long)(8 * g + 1) * n] = acc[b][4 * g + 1] + p0.y + p1.y + p2.y;
+        pp[(long)(8 * g + 2) * n] = acc[b][4 * g + 2] + p0.z + p1.z + p2.z;
+        pp[(long)(8 * g + 3) * n] = acc[b][4 * g + 3] + p0.w + p1.w + p2.w;
+      }
+    }
+  }
+}
+
+// Launches fc1's split-K form for m rows and returns its split count S (the
+// partials are [S][m][n1]): 64 x 64 tiles of a K quarter below 1024 rows
+// (batch 256: 128 workgroups), the wave-split-K form of a K half from there up.
+inline int launch_fc_splitk(const uint8_t* x, int m, int k, const int8_t* w1, int n1, int* part,
+                            hipStream_t st) {
   if (m < 1024) {
     const int tiles = (m / 64) * (n1 / 64) * FC_S;
     hipLaunchKernelGGL(fc_splitk_kernel<32>, dim3(tiles), dim3(256), 0, st, x, m, k, w1, n1, part);
-  } else {
-    const int tiles = (m / 128) * (n1 / 64) * FC_S;
-    hipLaunchKernelGGL(fc_splitk_kernel<64>, dim3(tiles), dim3(256), 0, st, x, m, k, w1, n1, part);
+    return FC_S;
   }
+  const int tiles = (m / 64) * (n1 / 64) * FC_S2;
+  // the flagship's k = 4096 (four load batches per wave) gets straight-line code
+  hipLaunchKernelGGL(k == 4096 ? fc_splitk_kernel_wavek<4> : fc_splitk_kernel_wavek<0>, dim3(tiles), dim3(256), 0,
+                     st, x, m, k, w1, n1, part);
+  return FC_S2;
 }
 
 struct FcHead {
@@ -149,6 +269,7 @@ struct FcHead {
   float y2_scale;
 };
 
+template <int S>   // split count of the partials
 __global__ __launch_bounds__(256) void fc_finish_kernel(const int* __restrict__ part, int m,
                                                         FcHead hd, uint8_t* __restrict__ y1,
                                                         uint8_t* __restrict__ y2,
@@ -158,9 +279,9 @@ __global__ __launch_bounds__(256) void fc_finish_kernel(const int* __restrict__ 
   if (row >= m) return;
   const int f0 = lane * 8;
   // every load up front (one wave per row: nothing else hides their latency)
-  int4 pv[FC_S][2];
+  int4 pv[S][2];
 #pragma unroll
-  for (int s = 0; s < FC_S; ++s) {
+  for (int s = 0; s < S; ++s) {
     const int* p = part + ((long)s * m + row) * FC_N1 + f0;
     pv[s][0] = *reinterpret_cast<const int4*>(p);
     pv[s][1] = *reinterpret_cast<const int4*>(p + 4);
@@ -176,7 +297,7 @@ __global__ __launch_bounds__(256) void fc_finish_kernel(const int* __restrict__ 
 
   int a[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
-  for (int s = 0; s < FC_S; ++s) {
+  for (int s = 0; s < S; ++s) {
     a[0] += pv[s][0].x; a[1] += pv[s][0].y; a[2] += pv[s][0].z; a[3] += pv[s][0].w;
     a[4] += pv[s][1].x; a[5] += pv[s][1].y; a[6] += pv[s][1].z; a[7] += pv[s][1].w;
   }
@@ -264,6 +385,7 @@ struct FcHeadQdq {
   int n2;
 };
 
+template <int S>   // split count of the partials
 __global__ __launch_bounds__(256) void fc_finish_qdq_kernel(const int* __restrict__ part, int m,
                                                             FcHeadQdq hd, uint8_t* __restrict__ y1,
                                                             float* __restrict__ y2f) {
@@ -271,9 +393,9 @@ __global__ __launch_bounds__(256) void fc_finish_qdq_kernel(const int* __restric
   const int row = blockIdx.x * 4 + wave;
   if (row >= m) return;
   const int f0 = lane * 8;
-  int4 pv[FC_S][2];
+  int4 pv[S][2];
 #pragma unroll
-  for (int s = 0; s < FC_S; ++s) {
+  for (int s = 0; s < S; ++s) {
     const int* p = part + ((long)s * m + row) * FC_N1 + f0;
     pv[s][0] = *reinterpret_cast<const int4*>(p);
     pv[s][1] = *reinterpret_cast<const int4*>(p + 4);
@@ -284,7 +406,7 @@ __global__ __launch_bounds__(256) void fc_finish_qdq_kernel(const int* __restric
   const float4 m0 = *reinterpret_cast<const float4*>(hd.m1 + f0), m4 = *reinterpret_cast<const float4*>(hd.m1 + f0 + 4);
   int a[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
 #pragma unroll
-  for (int s = 0; s < FC_S; ++s) {
+  for (int s = 0; s < S; ++s) {
     a[0] += pv[s][0].x; a[1] += pv[s][0].y; a[2] += pv[s][0].z; a[3] += pv[s][0].w;
     a[4] += pv[s][1].x; a[5] += pv[s][1].y; a[6] += pv[s][1].z; a[7] += pv[s][1].w;
   }
@@ -347,7 +469,7 @@ int qcn_pack_fc_kmajor(const int8_t* w, int n, int k, int8_t* out) {
 
 long long qcn_classifier_workspace_size(int m, int n1) {
   if (m <= 0 || n1 <= 0) return 0;
-  return (long long)qcn::FC_S * m * n1 * 4;   // the split-K partials
+  return (long long)qcn::FC_S * m * n1 * 4;   // the split-K partials at the larger split count
 }
 
 int qcn_classifier_u8s8(const uint8_t* x, int m, int k, const int8_t* w1, int n1, const float* u1,
@@ -367,9 +489,9 @@ int qcn_classifier_u8s8(const uint8_t* x, int m, int k, const int8_t* w1, int n1
   int* part = static_cast<int*>(workspace);
   qcn::FcHead hd{u1, v1, mult1, corr1, y1_zp, relu1 ? y1_zp : 0, w2, n2, u2, v2, mult2,
                  y2_zp, relu2 ? y2_zp : 0, y2_scale};
-  qcn::launch_fc_splitk(x, m, k, w1, n1, part, st);
-  hipLaunchKernelGGL(qcn::fc_finish_kernel, dim3((m + 3) / 4), dim3(256), 0, st, part, m, hd, y1,
-                     y2, y2f);
+  const int S = qcn::launch_fc_splitk(x, m, k, w1, n1, part, st);
+  hipLaunchKernelGGL(S == qcn::FC_S2 ? qcn::fc_finish_kernel<qcn::FC_S2> : qcn::fc_finish_kernel<qcn::FC_S>,
+                     dim3((m + 3) / 4), dim3(256), 0, st, part, m, hd, y1, y2, y2f);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 
@@ -387,9 +509,9 @@ int qcn_classifier_qdq_u8s8(const uint8_t* x, int m, int k, const int8_t* w1, in
   hipStream_t st = (hipStream_t)stream;
   int* part = static_cast<int*>(workspace);
   qcn::FcHeadQdq hd{u1, v1, mult1, corr1, y1_zp, 0, y1_scale, w2, b2, n2};
-  qcn::launch_fc_splitk(x, m, k, w1, n1, part, st);
-  hipLaunchKernelGGL(qcn::fc_finish_qdq_kernel, dim3((m + 3) / 4), dim3(256), 0, st, part, m, hd,
-                     y1, y2);
+  const int S = qcn::launch_fc_splitk(x, m, k, w1, n1, part, st);
+  hipLaunchKernelGGL(S == qcn::FC_S2 ? qcn::fc_finish_qdq_kernel<qcn::FC_S2> : qcn::fc_finish_qdq_kernel<qcn::FC_S>,
+                     dim3((m + 3) / 4), dim3(256), 0, st, part, m, hd, y1, y2);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 

@@ -286,7 +286,8 @@ int qcn_linear_u8s8(const uint8_t* x, int m, int k, int x_zp, const int8_t* w, i
                     int y_zp, int relu, uint8_t* y, float* y_deq, float y_scale, void* stream);
 
 /* A9 x 2 + A7 — the static classifier head in two launches: fc1 (+ReLU)
- * u8 x s8 -> u8 [m, n1] as a 4-way split-K GEMM into an int32 workspace, then
+ * u8 x s8 -> u8 [m, n1] as a split-K GEMM (2 partial planes from 1024 rows
+ * up, 4 below) into an int32 workspace, then
  * one wave per row finishes fc1 (requant) and computes fc2 (n2 <= 16) and its
  * DeQuantStub.  Same results as qcn_linear_u8s8(fc1) followed by
  * qcn_linear_u8s8(fc2, y_deq) — fc2's input zero point is y1_zp, fc2's
