@@ -6,6 +6,7 @@ Layers of this package:
   quant   host-side qparam / BN-fold / weight-quantization arithmetic
   qmodel  QuantizedConvNet: calibration, packing, the kernel sequence, graphs
   dist    one-process-per-GPU sharded inference with an RCCL logits all-gather
+  evaluate  top-1 / top-k, per-class and confusion counts kept on the device
 """
 from . import quant  # noqa: F401  (pure numpy, always importable)
 

@@ -51,6 +51,8 @@ SIGNATURES = {
     "qcn_histc_f32": (i32, [vp, i64, vp, i32, vp, vp]),
     "qcn_maxpool2x2_u8_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "qcn_argmax_f32": (i32, [vp, i32, i32, vp, vp]),
+    "qcn_eval_counters_len": (i64, [i32]),
+    "qcn_eval_topk_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "qcn_channel_affine_f32": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
     "qcn_conv3x3_packed_size": (i32, [i32, i32]),
     "qcn_pack_conv3x3_weight": (i32, [vp, i32, i32, vp, vp]),

@@ -91,6 +91,19 @@ def global_minmax(mm):
     return torch.stack([t[0], -t[1]])
 
 
+def sum_counts(t):
+    """All-reduce (SUM, in place) an int64 tensor of counts over the ranks and
+    return it; the identity at world size 1.  With it each rank scores its own
+    shard of a test set (evaluate.EvalCounts) and only 4 + 2*C integers (and
+    the confusion matrix, if kept) cross the fabric: no logits are gathered."""
+    if t.dtype != torch.int64:
+        raise TypeError(f"sum_counts: expected int64 counts, got {t.dtype}")
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return t
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
 def sharded_forward(model_fn, x_global, out=None):
     """Run ``model_fn`` on this rank's contiguous slice of ``x_global`` and
     all-gather the logits.  Requires the batch to divide evenly (fixed-shape

@@ -162,6 +162,51 @@ def argmax(x):
     return out
 
 
+def eval_counters_len(cols):
+    """Length of eval_topk's int64 counters for ``cols`` classes (4 + 2*cols)."""
+    n = lib().qcn_eval_counters_len(int(cols))
+    if n < 0:
+        raise ValueError("eval_counters_len: expected at least one class")
+    return n
+
+
+def eval_topk(logits, labels, k=5, counters=None, confusion=None, pred=None):
+    """ADDS the scores of fp32 ``logits`` [rows, cols] against int64 ``labels``
+    [rows] into ``counters`` (device int64 [4 + 2*cols]: rows, top-1 hits,
+    top-k hits, bad labels, per-class total, per-class top-1 correct; a zeroed
+    one is made when None) and, when given, into ``confusion`` (device int64
+    [cols, cols], cell [label, pred]); ``pred`` (device int64 [rows]) receives
+    the arg-max of every row.  The order and the tie rule are
+    qcn_eval_topk_f32's (include/qconvnet.h).  ``logits`` may start at any
+    4-byte boundary.  Returns ``counters``."""
+    _need(logits, torch.float32, "eval_topk.logits")
+    if logits.dim() != 2:
+        raise ValueError("eval_topk.logits: expected [rows, cols]")
+    rows, cols = logits.shape
+    _need(labels, torch.int64, "eval_topk.labels")
+    if labels.dim() != 1 or labels.numel() != rows:
+        raise ValueError("eval_topk.labels: expected one label per row")
+    need = eval_counters_len(cols)
+    if counters is None:
+        counters = torch.zeros(need, dtype=torch.int64, device=logits.device)
+    _need(counters, torch.int64, "eval_topk.counters")
+    if counters.numel() != need:
+        raise ValueError("eval_topk.counters: expected 4 + 2 * cols counts")
+    if confusion is not None:
+        _need(confusion, torch.int64, "eval_topk.confusion")
+        if confusion.numel() != cols * cols:
+            raise ValueError("eval_topk.confusion: expected [cols, cols]")
+    if pred is not None:
+        _need(pred, torch.int64, "eval_topk.pred")
+        if pred.numel() != rows:
+            raise ValueError("eval_topk.pred: expected one prediction per row")
+    if rows == 0:   # nothing to add (an empty tensor has no address to pass)
+        return counters
+    check(lib().qcn_eval_topk_f32(_ptr(logits), rows, cols, _ptr(labels), int(k), _ptr(counters),
+                                  _ptr(confusion), _ptr(pred), _stream()), "eval_topk")
+    return counters
+
+
 def channel_affine(x, alpha, beta, relu=False, out=None):
     """Inference BatchNorm1d (+ReLU) on [rows, cols] fp32: fma(x, alpha, beta)
     per column (alpha / beta from quant.bn_eval_affine)."""

@@ -109,6 +109,34 @@ int qcn_maxpool2x2_u8_nhwc(const uint8_t* x, int n, int h, int w, int c, uint8_t
  * NaN input is outside the contract. */
 int qcn_argmax_f32(const float* x, int rows, int cols, long long* idx, void* stream);
 
+/* The evaluator's scoring (utils/model_evaluator.py:36-46, 96-102, 160-168):
+ * top-1 / top-k hits, per-class totals and correct counts, the confusion
+ * matrix and the predictions of fp32 logits [rows, cols] against int64 labels,
+ * without the logits leaving the device.
+ * Order: NaN above everything and all NaNs equal, -0.0 == +0.0, otherwise the
+ * usual order with +-inf as values (torch's for max / argmax / topk).  For a
+ * row x with label l:
+ *   rank = #{ j : x[j] > x[l]  or  (x[j] == x[l] and j < l) }
+ *   top-k hit iff rank < k, top-1 hit iff rank == 0  (a stable descending sort
+ *   on ties; torch.topk's tie order is unspecified);
+ *   pred = the lowest j whose value is maximal (torch.argmax, NaN included).
+ * A label outside [0, cols) makes the row a miss: it is counted in rows and
+ * bad_labels and in no class bin or confusion cell.  k > cols is legal (every
+ * in-range label hits).
+ * int64 counters[qcn_eval_counters_len(cols) = 4 + 2*cols]:
+ *   [0] rows seen  [1] top-1 hits  [2] top-k hits  [3] rows with a bad label
+ *   [4 .. 4+cols)        per-class total   (indexed by label)
+ *   [4+cols .. 4+2cols)  per-class top-1 correct
+ * confusion (nullable): int64 [cols][cols], cell [label][pred];
+ * pred (nullable): int64 [rows].
+ * ADDS into counters and confusion with 64-bit integer atomics (the caller
+ * zeroes them once; calls on several streams may share them).  logits need
+ * 4-byte alignment only.  QCN_ERR_ARG for a null logits / labels / counters,
+ * rows < 0, cols < 1 or k < 1; rows == 0 launches nothing. */
+long long qcn_eval_counters_len(int cols);
+int qcn_eval_topk_f32(const float* logits, int rows, int cols, const long long* labels, int k,
+                      long long* counters, long long* confusion, long long* pred, void* stream);
+
 /* Inference BatchNorm1d (+ReLU) on fp32 [rows, cols] (bn7 of the reference's
  * StaticPTQModel between its dynamic fc1 and fc2, models/static_ptq_model.py:
  * 19-34 over baseline_model.py:80-82): y = fma(x, alpha[c], beta[c]), then
