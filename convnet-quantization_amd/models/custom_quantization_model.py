@@ -64,6 +64,17 @@ class CustomQuantizationModel(nn.Module):
         self.quantized_model = QuantizedConvNet(spec, self.device, mean=mean, std=std)
         return self.quantized_model
 
+    def quantization_report(self, images, batch=256):
+        """Per-layer quantization error of ``images`` (fp32 NCHW or raw uint8
+        NHWC) at every QDQ hand-off: qconvnet.qerror.layer_report of the int8
+        model against the BN-folded fp32 ``model``."""
+        if self.quantized_model is None:
+            raise RuntimeError("quantization_report: call quantize() first")
+        from qconvnet.qerror import layer_report
+        self.model.eval()
+        folded = fold_state_dict(self.model.state_dict())
+        return layer_report(self.quantized_model, folded, images, batch)
+
     def forward(self, x):
         if self.quantized_model is not None:
             return self.quantized_model(x)

@@ -61,6 +61,19 @@ class StaticPTQModel:
         self.quantized_model = QuantizedConvNet(spec, self.device, mean=mean, std=std)
         return self.quantized_model
 
+    def quantization_report(self, images, batch=256):
+        """Per-layer quantization error of ``images`` (fp32 NCHW or raw uint8
+        NHWC): {layer: per-channel and whole-tensor SQNR, clipping and rounding
+        statistics} — qconvnet.qerror.layer_report of the int8 model against
+        the BN-folded ``fp32_model``.  The reference prints one
+        torch.abs(fp32_output - int8_output).mean() (static_ptq_model.py:93-95)."""
+        if not isinstance(self.quantized_model, QuantizedConvNet):
+            raise RuntimeError("quantization_report: call quantize() first (mode='static')")
+        from qconvnet.qerror import layer_report
+        self.fp32_model.eval()
+        folded = fold_state_dict(self.fp32_model.state_dict())
+        return layer_report(self.quantized_model, folded, images, batch)
+
     def get_model_size(self, model):
         """MB of the serialized parameters (the reference writes temp_model.pth
         into the CWD, static_ptq_model.py:36-43; this uses an in-memory buffer)."""

@@ -7,6 +7,7 @@ Layers of this package:
   qmodel  QuantizedConvNet: calibration, packing, the kernel sequence, graphs
   dist    one-process-per-GPU sharded inference with an RCCL logits all-gather
   evaluate  top-1 / top-k, per-class and confusion counts kept on the device
+  qerror  per-layer quantization error (SQNR, clipping, rounding) on the device
 """
 from . import quant  # noqa: F401  (pure numpy, always importable)
 

@@ -53,6 +53,8 @@ SIGNATURES = {
     "qcn_argmax_f32": (i32, [vp, i32, i32, vp, vp]),
     "qcn_eval_counters_len": (i64, [i32]),
     "qcn_eval_topk_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
+    "qcn_qerror_workspace_size": (i64, [i32, i32, i32, i32]),
+    "qcn_qerror_u8_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
     "qcn_channel_affine_f32": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
     "qcn_conv3x3_packed_size": (i32, [i32, i32]),
     "qcn_pack_conv3x3_weight": (i32, [vp, i32, i32, vp, vp]),

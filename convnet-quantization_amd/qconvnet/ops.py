@@ -207,6 +207,60 @@ def eval_topk(logits, labels, k=5, counters=None, confusion=None, pred=None):
     return counters
 
 
+def qerror_workspace_size(n, c, h, w):
+    """Bytes of qerror's workspace for an [n,c,h,w] activation (host arithmetic)."""
+    size = lib().qcn_qerror_workspace_size(int(n), int(c), int(h), int(w))
+    if size < 0:
+        raise ValueError(f"qerror_workspace_size: bad shape {(n, c, h, w)} ({size})")
+    return size
+
+
+def qerror_buffers(channels, device):
+    """Zeroed (counts int64 [channels, 5], sums float64 [channels, 3]) for qerror."""
+    return (torch.zeros((int(channels), 5), dtype=torch.int64, device=device),
+            torch.zeros((int(channels), 3), dtype=torch.float64, device=device))
+
+
+def qerror(x, q, scale, zero_point, counts, sums, nhwc=True, workspace=None):
+    """ADDS the per-channel error statistics of the u8 activation ``q``
+    (qparams ``scale``, ``zero_point``; NHWC [n,h,w,c] when ``nhwc`` else
+    NCHW; [rows, c] either way) against its fp32 reference ``x`` (NCHW
+    [n,c,h,w] or [rows, c]) into ``counts`` / ``sums`` (qerror_buffers; the
+    fields are qcn_qerror_u8_f32's, include/qconvnet.h).  ``x`` may start at
+    any 4-byte boundary, ``q`` at any byte.  ``workspace``: a device uint8
+    tensor of at least qerror_workspace_size bytes (one is made when None;
+    concurrent streams need their own, and their own ``sums``).  No sync.
+    Returns the workspace."""
+    _need(x, torch.float32, "qerror.x")
+    _need(q, torch.uint8, "qerror.q")
+    if x.dim() == 2:
+        n, c = x.shape
+        h = w = 1
+    elif x.dim() == 4:
+        n, c, h, w = x.shape
+    else:
+        raise ValueError("qerror.x: expected [n,c,h,w] or [rows,c]")
+    want = (n, c) if x.dim() == 2 else ((n, h, w, c) if nhwc else (n, c, h, w))
+    if tuple(q.shape) != want:
+        raise ValueError(f"qerror.q: expected shape {want}, got {tuple(q.shape)}")
+    _need(counts, torch.int64, "qerror.counts")
+    _need(sums, torch.float64, "qerror.sums")
+    if counts.numel() != 5 * c or sums.numel() != 3 * c:
+        raise ValueError("qerror: expected counts [c, 5] and sums [c, 3]")
+    need = qerror_workspace_size(n, c, h, w)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    _need(workspace, torch.uint8, "qerror.workspace")
+    if workspace.numel() < need:
+        raise ValueError(f"qerror.workspace: {need} bytes needed")
+    if n == 0:   # nothing to add (an empty tensor has no address to pass)
+        return workspace
+    check(lib().qcn_qerror_u8_f32(_ptr(x), _ptr(q), n, c, h, w, int(bool(nhwc)), float(scale),
+                                  int(zero_point), _ptr(counts), _ptr(sums), _ptr(workspace),
+                                  _stream()), "qerror")
+    return workspace
+
+
 def channel_affine(x, alpha, beta, relu=False, out=None):
     """Inference BatchNorm1d (+ReLU) on [rows, cols] fp32: fma(x, alpha, beta)
     per column (alpha / beta from quant.bn_eval_affine)."""

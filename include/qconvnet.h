@@ -137,6 +137,36 @@ long long qcn_eval_counters_len(int cols);
 int qcn_eval_topk_f32(const float* logits, int rows, int cols, const long long* labels, int k,
                       long long* counters, long long* confusion, long long* pred, void* stream);
 
+/* Quantization error of a u8 activation against its fp32 reference, per
+ * channel (the reference prints one torch.abs(fp32 - int8).mean() per model,
+ * models/static_ptq_model.py:93-95; torch.ao.ns compute_sqnr per tensor).
+ * x: fp32 NCHW [n,c,h,w] ([rows,c] is h = w = 1); q: u8 with qparams (scale,
+ * zero_point), NHWC when nhwc_q != 0 else NCHW.  Per element, IEEE fp32 with
+ * nothing contracted unless it says double:
+ *   d = scale * float(int(q) - zp);  lo = scale * float(0 - zp);
+ *   hi = scale * float(255 - zp);    e = double(x) - double(d);
+ *   qref = clamp(zp + rne(x * fp32(1/scale)), 0, 255)   (qcn_quantize_f32_u8).
+ * int64 counts[c][5]: elements, #(x < lo), #(x > hi), #(qref != q), and the
+ * fp32 bit pattern of max fabsf(x - d), zero-extended (non-negative floats
+ * order as their bits do).  double sums[c][3]: sum double(x)^2, sum e^2,
+ * sum |e|.  NaN / +-inf in x are outside the contract.
+ * ADDS into counts (64-bit integer atomics) and sums (no floating-point
+ * atomics: per-workgroup partials in `workspace`, added in a fixed order by a
+ * finishing launch, so the same calls on one stream give the same bits; the
+ * caller zeroes counts and sums once; concurrent streams each need their own
+ * sums and workspace).  workspace: device memory of
+ * qcn_qerror_workspace_size(n,c,h,w) bytes, 8-byte aligned, no initialisation
+ * needed; the size is host arithmetic (0 for n == 0, a negative status for a
+ * bad shape).  x needs 4-byte alignment, q none (16-byte accesses where both
+ * the pointer and the shape allow).  1 <= c <= 65536 and n*h*w < 2^31, else
+ * QCN_ERR_UNSUPPORTED; QCN_ERR_ARG for a null pointer, n < 0, c / h / w < 1,
+ * zero_point outside [0,255] or a scale that is not finite and positive —
+ * checked before any device call; n == 0 launches nothing. */
+long long qcn_qerror_workspace_size(int n, int c, int h, int w);
+int qcn_qerror_u8_f32(const float* x, const uint8_t* q, int n, int c, int h, int w, int nhwc_q,
+                      float scale, int zero_point, long long* counts, double* sums,
+                      void* workspace, void* stream);
+
 /* Inference BatchNorm1d (+ReLU) on fp32 [rows, cols] (bn7 of the reference's
  * StaticPTQModel between its dynamic fc1 and fc2, models/static_ptq_model.py:
  * 19-34 over baseline_model.py:80-82): y = fma(x, alpha[c], beta[c]), then
