@@ -85,6 +85,22 @@ struct GemmArgs {
   uint8_t* y2;
 };
 
+// Form query (qcn_conv_gemm_form / qcn_conv1x1_join_reduce_form): while a
+// probe is set on the calling thread, the launchers record the instantiation
+// they were reached with and return QCN_OK in place of launching, so the query
+// (which calls the launch entry itself, at the end of this file) walks the
+// launch's own checks and dispatch.  Host state only: GemmArgs, and with it
+// every kernel, is unchanged.
+struct FormProbe {
+  qcn_conv_form_t* out;
+  bool device;   // nchunk / per wanted: CU count and occupancy of the current device
+};
+static thread_local FormProbe* t_probe = nullptr;
+struct ProbeScope {
+  explicit ProbeScope(FormProbe* p) { t_probe = p; }
+  ~ProbeScope() { t_probe = nullptr; }
+};
+
 template <int BN, int BM_ = 256>
 struct GemmCfg {
   // BM_ = 128 (thin convs, K <= 256): half the pixels per tile, 64 accumulators
@@ -471,6 +487,13 @@ int launch_gemm(GemmArgs& a, hipStream_t st) {
   using C = GemmCfg<BN, BM>;
   a.mt = (int)((a.npix + C::BM - 1) / C::BM);
   a.nt = a.cout / BN;
+  if (t_probe) {
+    // rq / zo: the kernel's run-time epilogue branches (fast, lo == 0, general;
+    // the join's z_o == 0)
+    *t_probe->out = qcn_conv_form_t{QCN_CONV_TILED, BN, C::NW, a.zp_y == 0 ? 0 : (a.lo == 0 ? 1 : 2),
+                                    RESID ? (a.z_o == 0 ? 1 : 0) : -1, 0, 0, 0, 0, 0, 0, 0};
+    return QCN_OK;
+  }
   static bool attr_done[QCN_MAX_DEV] = {};
   if (!qcn_set_lds_once((const void*)conv_gemm_kernel<BN, RESID, BM>, C::LDS, attr_done))
     return QCN_ERR_HIP;
@@ -908,20 +931,28 @@ template <int K, int NW, bool RESID, int P, int RQ, int ZO, bool BL, bool S2 = f
 int launch_stream(GemmArgs& a, hipStream_t st) {
   const auto kern = conv1x1_stream_kernel<K, NW, RESID, P, RQ, ZO, BL, S2, CR>;
   static int occ_dev[QCN_MAX_DEV] = {};
-  const int d = qcn_current_device(), ncu = qcn_cu_count();
-  if (d < 0 || ncu <= 0) return QCN_ERR_HIP;
-  int& occ = occ_dev[d];
-  if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NW * 64, 0) != hipSuccess || occ <= 0))
-    return QCN_ERR_HIP;
   a.cg = a.cout / (32 * NW);
   a.nstrip = (int)((a.npix + 31) / 32);
-  // one resident wave of workgroups: cg x nchunk ~ CUs x occupancy, chunks a
-  // multiple of 8 (the XCD interleave of blockIdx)
-  int nchunk = (ncu * occ) / a.cg;
-  nchunk = nchunk < 8 ? 8 : nchunk & ~7;
-  if (nchunk > a.nstrip) nchunk = a.nstrip;
-  a.per = (a.nstrip + nchunk - 1) / nchunk;
-  a.nchunk = (a.nstrip + a.per - 1) / a.per;
+  a.per = a.nchunk = -1;
+  if (!t_probe || t_probe->device) {   // (a form query may ask without the device)
+    const int d = qcn_current_device(), ncu = qcn_cu_count();
+    if (d < 0 || ncu <= 0) return QCN_ERR_HIP;
+    int& occ = occ_dev[d];
+    if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, NW * 64, 0) != hipSuccess || occ <= 0))
+      return QCN_ERR_HIP;
+    // one resident wave of workgroups: cg x nchunk ~ CUs x occupancy, chunks a
+    // multiple of 8 (the XCD interleave of blockIdx)
+    int nchunk = (ncu * occ) / a.cg;
+    nchunk = nchunk < 8 ? 8 : nchunk & ~7;
+    if (nchunk > a.nstrip) nchunk = a.nstrip;
+    a.per = (a.nstrip + nchunk - 1) / nchunk;
+    a.nchunk = (a.nstrip + a.per - 1) / a.per;
+  }
+  if (t_probe) {
+    *t_probe->out = qcn_conv_form_t{CR > 0 ? QCN_CONV_JOIN_REDUCE : (S2 ? QCN_CONV_STREAM_S2 : QCN_CONV_STREAM),
+                                    0, NW, RQ, RESID ? ZO : -1, K, P, BL ? 1 : 0, CR, a.nstrip, a.nchunk, a.per};
+    return QCN_OK;
+  }
   const int grid = (a.nchunk + 7) / 8 * 8 * a.cg;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), 0, st, a);
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
@@ -1233,6 +1264,10 @@ __global__ __launch_bounds__((ImgCfg<HW, CIN, NS>::NT), 1) void conv3x3_img_kern
 template <int HW, int CIN, int D, int NS>
 int launch_img(GemmArgs& a, hipStream_t st) {
   using C = ImgCfg<HW, CIN, NS>;
+  if (t_probe) {   // one epilogue: the general clamp (requant_f)
+    *t_probe->out = qcn_conv_form_t{QCN_CONV_IMG, 0, C::NW, 2, -1, 0, 0, 0, 0, 0, 0, 0};
+    return QCN_OK;
+  }
   static bool attr_done[QCN_MAX_DEV] = {};
   if (!qcn_set_lds_once((const void*)conv3x3_img_kernel<HW, CIN, D, NS>, C::LDS, attr_done)) return QCN_ERR_HIP;
   hipLaunchKernelGGL((conv3x3_img_kernel<HW, CIN, D, NS>), dim3(a.n * (a.cout / C::COUT)), dim3(C::NT), C::LDS, st,
@@ -1384,4 +1419,43 @@ extern "C" int qcn_conv_gemm_u8s8_nhwc(const uint8_t* x, int nimg, int h, int w,
   if (cout % 128 == 0)
     return resid ? qcn::launch_gemm<128, true>(a, st) : qcn::launch_gemm<128, false>(a, st);
   return resid ? qcn::launch_gemm<64, true>(a, st) : qcn::launch_gemm<64, false>(a, st);
+}
+
+// ---- form queries: the entry points above, argument checks and dispatch
+// included, under a probe (FormProbe).  One host address stands for every
+// tensor: under a probe nothing is dereferenced and nothing is launched.
+namespace {
+alignas(16) unsigned char g_no_tensor[16];
+template <class T>
+T* no_tensor() { return reinterpret_cast<T*>(g_no_tensor); }
+}  // namespace
+
+extern "C" int qcn_conv_gemm_form(int nimg, int h, int w, int cin, int x_zp, int cout, int kh, int kw,
+                                  int stride_h, int stride_w, int pad_h, int pad_w, int y_zp, int relu,
+                                  int has_resid, float y_scale, float r_scale, int r_zp, float out_scale,
+                                  int out_zp, int use_device, qcn_conv_form_t* form) {
+  if (!form) return QCN_ERR_ARG;
+  *form = qcn_conv_form_t{};
+  qcn::FormProbe probe{form, use_device != 0};
+  qcn::ProbeScope scope(&probe);
+  return qcn_conv_gemm_u8s8_nhwc(no_tensor<uint8_t>(), nimg, h, w, cin, x_zp, no_tensor<int8_t>(), cout, kh, kw,
+                                 stride_h, stride_w, pad_h, pad_w, no_tensor<float>(), no_tensor<float>(),
+                                 no_tensor<float>(), no_tensor<int32_t>(), y_zp, relu,
+                                 has_resid ? no_tensor<uint8_t>() : nullptr, y_scale, r_scale, r_zp, out_scale,
+                                 out_zp, no_tensor<uint8_t>(), nullptr);
+}
+
+extern "C" int qcn_conv1x1_join_reduce_form(int nimg, int h, int w, int cin, int x_zp, int cout, int y_zp,
+                                            float y_scale, float r_scale, int r_zp, float out_scale, int out_zp,
+                                            int cout2, int y2_zp, int relu2, int use_device,
+                                            qcn_conv_form_t* form) {
+  if (!form) return QCN_ERR_ARG;
+  *form = qcn_conv_form_t{};
+  qcn::FormProbe probe{form, use_device != 0};
+  qcn::ProbeScope scope(&probe);
+  return qcn_conv1x1_join_reduce_u8s8_nhwc(
+      no_tensor<uint8_t>(), nimg, h, w, cin, x_zp, no_tensor<int8_t>(), cout, no_tensor<float>(),
+      no_tensor<float>(), no_tensor<float>(), no_tensor<int32_t>(), y_zp, no_tensor<uint8_t>(), y_scale, r_scale,
+      r_zp, out_scale, out_zp, no_tensor<uint8_t>(), no_tensor<int8_t>(), cout2, no_tensor<float>(),
+      no_tensor<float>(), no_tensor<float>(), no_tensor<int32_t>(), y2_zp, relu2, no_tensor<uint8_t>(), nullptr);
 }

@@ -36,6 +36,13 @@ class ConvLayer(C.Structure):
                 ("qdq", C.POINTER(QDQ))]
 
 
+class ConvForm(C.Structure):
+    """qcn_conv_form_t"""
+    FAMILIES = {1: "stream", 2: "stream_s2", 3: "join_reduce", 4: "img", 5: "tiled"}
+    _fields_ = [(k, C.c_int32) for k in ("family", "bn", "nw", "rq", "zo", "k", "p", "bl", "cr", "nstrip",
+                                         "nchunk", "per")]
+
+
 vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_longlong
@@ -108,6 +115,10 @@ SIGNATURES = {
     "qcn_conv1x1_join_reduce_u8s8_nhwc": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, vp,
                                                 f32, f32, i32, f32, i32, vp, vp, i32, vp, vp, vp, vp, i32,
                                                 i32, vp, vp]),
+    "qcn_conv_gemm_form": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32,
+                                 f32, f32, i32, f32, i32, i32, C.POINTER(ConvForm)]),
+    "qcn_conv1x1_join_reduce_form": (i32, [i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, f32, i32, i32,
+                                           i32, i32, i32, C.POINTER(ConvForm)]),
     "qcn_add_relu_u8": (i32, [vp, f32, i32, vp, f32, i32, i64, f32, i32, i32, vp, vp]),
     "qcn_maxpool3x3s2_u8_nhwc": (i32, [vp, i32, i32, i32, i32, vp, vp]),
     "qcn_stem_pack_f32_nchw": (i32, [vp, i32, i32, i32, f32, i32, vp, vp]),

@@ -740,6 +740,50 @@ def conv_join_reduce(x, x_zp, layer, resid, nxt, out=None, out2=None):
     return out, out2
 
 
+def _form_dict(f):
+    d = {k: int(getattr(f, k)) for k, _ in _lib.ConvForm._fields_}
+    d["family"] = _lib.ConvForm.FAMILIES[d["family"]]
+    return d
+
+
+def conv_gemm_form(shape, x_zp, layer, resid=None, device=False):
+    """Host query (no launch, no tensors): what ``conv(x, x_zp, layer,
+    resid=resid)`` launches on the GEMM path for ``x`` of ``shape`` (n, h, w,
+    cin) — a dict of qcn_conv_form_t's fields (family as a name: stream,
+    stream_s2, img, tiled), decided by the launch's own dispatch.  ``resid`` as
+    for conv() (its tensor is ignored and may be None).  With ``device`` the
+    strip plan of the streaming kernel on the current device (nchunk, per) is
+    filled in; without, no device is touched and both are -1."""
+    n, h, w, cin = (int(t) for t in shape)
+    d = layer
+    if resid is not None:
+        _, s_r, z_r, s_o, z_o = resid
+        sy_, has = float(d.s_y), 1
+    else:
+        sy_, s_r, z_r, s_o, z_o, has = 0.0, 0.0, 0, 0.0, 0, 0
+    f = _lib.ConvForm()
+    check(lib().qcn_conv_gemm_form(n, h, w, cin, int(x_zp), d.cout, d.kh, d.kw, d.sy, d.sx, d.py, d.px,
+                                   int(d.z_y), int(bool(d.relu)), has, sy_, float(s_r), int(z_r),
+                                   float(s_o), int(z_o), int(bool(device)), C.byref(f)), "conv_gemm_form")
+    return _form_dict(f)
+
+
+def conv_join_reduce_form(shape, x_zp, layer, resid, nxt, device=False):
+    """conv_gemm_form() for ``conv_join_reduce(x, x_zp, layer, resid, nxt)``
+    (family join_reduce); None where conv_join_reduce() returns None."""
+    n, h, w, cin = (int(t) for t in shape)
+    d, e = layer, nxt
+    _, s_r, z_r, s_o, z_o = resid
+    f = _lib.ConvForm()
+    rc = lib().qcn_conv1x1_join_reduce_form(n, h, w, cin, int(x_zp), d.cout, int(d.z_y), float(d.s_y),
+                                            float(s_r), int(z_r), float(s_o), int(z_o), e.cout, int(e.z_y),
+                                            int(bool(e.relu)), int(bool(device)), C.byref(f))
+    if rc == _lib.QCN_ERR_UNSUPPORTED:
+        return None
+    check(rc, "conv_join_reduce_form")
+    return _form_dict(f)
+
+
 def add_relu(a, sa, za, b, sb, zb, s_out, z_out, relu=True, out=None):
     _need(a, torch.uint8, "add.a")
     _need(b, torch.uint8, "add.b")

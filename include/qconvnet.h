@@ -473,6 +473,50 @@ int qcn_conv1x1_join_reduce_u8s8_nhwc(const uint8_t* x, int nimg, int h, int w, 
                                       uint8_t* y, const int8_t* w2_packed, int cout2, const float* u2,
                                       const float* v2, const float* mult2, const int32_t* corr2, int y2_zp,
                                       int relu2, uint8_t* y2, void* stream);
+/* What qcn_conv_gemm_u8s8_nhwc / qcn_conv1x1_join_reduce_u8s8_nhwc launch for
+ * a set of arguments (qcn_conv_gemm_form, qcn_conv1x1_join_reduce_form). */
+#define QCN_CONV_STREAM 1       /* conv1x1_stream_kernel, stride 1                */
+#define QCN_CONV_STREAM_S2 2    /* conv1x1_stream_kernel, the stride-2 downsample */
+#define QCN_CONV_JOIN_REDUCE 3  /* conv1x1_stream_kernel with the fused reduce    */
+#define QCN_CONV_IMG 4          /* conv3x3_img_kernel (whole image per workgroup) */
+#define QCN_CONV_TILED 5        /* conv_gemm_kernel (256-pixel tiles)             */
+typedef struct qcn_conv_form_t {
+  int32_t family; /* QCN_CONV_*                                                    */
+  int32_t bn;     /* tiled: output channels per workgroup (64 / 128 / 256), else 0 */
+  int32_t nw;     /* waves per workgroup                                           */
+  int32_t rq;     /* requant form: 0 z_y == 0 and no ReLU floor (the saturating
+                     pack alone), 1 no ReLU floor (rint + z_y, saturating pack),
+                     2 the general clamp; the tiled kernel's three branches in the
+                     same order (0 also with ReLU: the floor is 0 there); the
+                     whole-image kernel has the general clamp only                 */
+  int32_t zo;     /* join form: 0 out_zp != 0, 1 out_zp == 0, 2 out_zp == 0 in the
+                     one-fma form (qcn_join_affine; streaming families only);
+                     -1 without a join                                             */
+  int32_t k;      /* streaming families: the compiled-in K, else 0                 */
+  int32_t p;      /* streaming families: prefetch ring depth in strips, else 0     */
+  int32_t bl;     /* streaming families: 1 activations through the LDS ring        */
+  int32_t cr;     /* fused reduce: its output channels, else 0                     */
+  int32_t nstrip; /* streaming families: 32-pixel strips, else 0                   */
+  int32_t nchunk; /* streaming families: chunks (workgroups per channel group) and */
+  int32_t per;    /*   strips per chunk; both -1 when asked without the device     */
+} qcn_conv_form_t;
+/* Host query (no launch, no tensors): the form qcn_conv_gemm_u8s8_nhwc takes
+ * for these shape and quantization arguments (has_resid: whether resid would
+ * be non-NULL).  It runs the launch's own argument checks and dispatch with
+ * the launchers recording instead of launching, so it returns what the launch
+ * would return before any device work (QCN_OK and *form filled, or
+ * QCN_ERR_ARG / QCN_ERR_UNSUPPORTED).  use_device == 0: no HIP call is made
+ * and nchunk / per, which depend on the device's CU count and the kernel's
+ * occupancy, are -1; otherwise they are those of the current device
+ * (QCN_ERR_HIP without one). */
+int qcn_conv_gemm_form(int nimg, int h, int w, int cin, int x_zp, int cout, int kh, int kw, int stride_h,
+                       int stride_w, int pad_h, int pad_w, int y_zp, int relu, int has_resid, float y_scale,
+                       float r_scale, int r_zp, float out_scale, int out_zp, int use_device,
+                       qcn_conv_form_t* form);
+/* The same for qcn_conv1x1_join_reduce_u8s8_nhwc. */
+int qcn_conv1x1_join_reduce_form(int nimg, int h, int w, int cin, int x_zp, int cout, int y_zp, float y_scale,
+                                 float r_scale, int r_zp, float out_scale, int out_zp, int cout2, int y2_zp,
+                                 int relu2, int use_device, qcn_conv_form_t* form);
 /* Residual join (custom_quantization_model.py:94-101 then the next stage's
  * QuantStub): y = quantize(relu?(fp32(sa*(a-za)) + fp32(sb*(b-zb))), s_out, z_out).
  * Any byte alignment: 16-byte accesses when a, b and y are all 16-byte
