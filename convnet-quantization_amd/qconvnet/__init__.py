@@ -8,6 +8,7 @@ Layers of this package:
   dist    one-process-per-GPU sharded inference with an RCCL logits all-gather
   evaluate  top-1 / top-k, per-class and confusion counts kept on the device
   qerror  per-layer quantization error (SQNR, clipping, rounding) on the device
+  preprocess  Resize -> CenterCrop of raw u8 images of mixed sizes on the device
 """
 from . import quant  # noqa: F401  (pure numpy, always importable)
 

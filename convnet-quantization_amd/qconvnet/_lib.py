@@ -43,6 +43,11 @@ class ConvForm(C.Structure):
                                          "nchunk", "per")]
 
 
+class ResizeImg(C.Structure):
+    """qcn_resize_img_t (numpy: qconvnet.preprocess.DESC)"""
+    _fields_ = [("offset", C.c_longlong)] + [(k, C.c_int32) for k in ("h", "w", "oh", "ow", "top", "left")]
+
+
 vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_longlong
@@ -62,6 +67,9 @@ SIGNATURES = {
     "qcn_eval_topk_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "qcn_qerror_workspace_size": (i64, [i32, i32, i32, i32]),
     "qcn_qerror_u8_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
+    "qcn_resize_crop_workspace_size": (i64, [C.POINTER(ResizeImg), i32, i32, i32]),
+    "qcn_resize_crop_tap_stride": (i32, [C.POINTER(ResizeImg), i32, i32, i32]),
+    "qcn_resize_crop_u8_hwc": (i32, [vp, i64, C.POINTER(ResizeImg), vp, i32, i32, i32, vp, vp, vp]),
     "qcn_channel_affine_f32": (i32, [vp, i32, i32, vp, vp, i32, vp, vp]),
     "qcn_conv3x3_packed_size": (i32, [i32, i32]),
     "qcn_pack_conv3x3_weight": (i32, [vp, i32, i32, vp, vp]),

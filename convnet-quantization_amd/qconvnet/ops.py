@@ -261,6 +261,59 @@ def qerror(x, q, scale, zero_point, counts, sums, nhwc=True, workspace=None):
     return workspace
 
 
+def _resize_desc(desc):
+    from .preprocess import DESC
+    if not isinstance(desc, np.ndarray) or desc.dtype != DESC or desc.ndim != 1:
+        raise ValueError("resize_crop.desc: expected a 1-D numpy array of preprocess.DESC")
+    desc = np.ascontiguousarray(desc)
+    return desc, desc.ctypes.data_as(C.POINTER(_lib.ResizeImg))
+
+
+def resize_crop_workspace_size(desc, ch, cw):
+    """(bytes of resize_crop's workspace, int32 words per tap record) for the
+    descriptors ``desc`` (preprocess.plan) and a [ch, cw] window; host
+    arithmetic.  Raises ValueError for a bad descriptor or an image outside
+    the tap envelope."""
+    desc, p = _resize_desc(desc)
+    size = lib().qcn_resize_crop_workspace_size(p, len(desc), int(ch), int(cw))
+    if size < 0:
+        raise ValueError(f"resize_crop: {_lib._ERRS.get(size, 'error')} ({size})")
+    return size, lib().qcn_resize_crop_tap_stride(p, len(desc), int(ch), int(cw))
+
+
+def resize_crop(src, desc, desc_dev, ch, cw, out=None, workspace=None):
+    """Resample every image of the packed u8 device buffer ``src`` and write
+    its [ch, cw] window to ``out`` (u8 [n, ch, cw, 3]; made when None), byte
+    for byte Pillow's bilinear resize + crop (qcn_resize_crop_u8_hwc,
+    include/qconvnet.h).  ``desc``: the host descriptors (preprocess.plan);
+    ``desc_dev``: the same bytes in device memory.  ``src`` may start at any
+    byte.  ``workspace``: a device uint8 tensor of at least
+    resize_crop_workspace_size bytes (made when None).  No sync.  Returns
+    (out, workspace)."""
+    _need(src, torch.uint8, "resize_crop.src")
+    _need(desc_dev, torch.uint8, "resize_crop.desc_dev")
+    desc, p = _resize_desc(desc)
+    n, ch, cw = len(desc), int(ch), int(cw)
+    if desc_dev.numel() != desc.nbytes:
+        raise ValueError("resize_crop.desc_dev: expected the bytes of desc")
+    need, _ = resize_crop_workspace_size(desc, ch, cw)
+    if out is None:
+        out = torch.empty((n, ch, cw, 3), dtype=torch.uint8, device=src.device)
+    _need(out, torch.uint8, "resize_crop.out")
+    if out.numel() != n * ch * cw * 3:
+        raise ValueError("resize_crop.out: expected [n, ch, cw, 3]")
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=src.device)
+    _need(workspace, torch.uint8, "resize_crop.workspace")
+    if workspace.numel() < need:
+        raise ValueError(f"resize_crop.workspace: {need} bytes needed")
+    if n == 0:   # nothing to launch (an empty tensor has no address to pass)
+        return out, workspace
+    check(lib().qcn_resize_crop_u8_hwc(_ptr(src), src.numel(), p, _ptr(desc_dev), n, ch, cw, _ptr(out),
+                                       _ptr(workspace), _stream()), "resize_crop")
+    return out, workspace
+
+
 def channel_affine(x, alpha, beta, relu=False, out=None):
     """Inference BatchNorm1d (+ReLU) on [rows, cols] fp32: fma(x, alpha, beta)
     per column (alpha / beta from quant.bn_eval_affine)."""

@@ -167,6 +167,49 @@ int qcn_qerror_u8_f32(const float* x, const uint8_t* q, int n, int c, int h, int
                       float scale, int zero_point, long long* counts, double* sums,
                       void* workspace, void* stream);
 
+/* Resize(R) -> CenterCrop(C) of raw u8 images of mixed sizes (the ImageNet
+ * transform, utils/dataset_manager.py:24-25), byte for byte what Pillow's
+ * bilinear Image.resize followed by a crop gives.
+ * src: one packed device buffer; image i is u8 HWC [h][w][3] at src + offset
+ * and is resampled to (oh, ow), of which the window [top, top+ch) x
+ * [left, left+cw) is written to y[i] (u8 HWC [ch][cw][3]); only that window
+ * is computed.  src, y and the offsets may have any byte alignment.
+ * Per axis, `in` samples become `out` samples (IEEE double, nothing
+ * contracted; (int) truncates):
+ *   scale = in / out;  fs = max(scale, 1.0);  support = 1.0 * fs;  ss = 1.0 / fs
+ *   center = (xx + 0.5) * scale
+ *   xmin = max((int)(center - support + 0.5), 0)
+ *   xmax = min((int)(center + support + 0.5), in)
+ *   w[i] = max(0.0, 1.0 - fabs((i + xmin - center + 0.5) * ss)),  i < xmax - xmin
+ *   ww = w[0] + w[1] + ...;  k[i] = (int)(0.5 + (w[i] / ww) * 4194304.0)
+ *   y[xx] = clamp((sum_i x[xmin + i] * k[i] + (1 << 21)) >> 22, 0, 255)   (int32)
+ * The horizontal pass runs first and rounds to u8; the vertical pass reads
+ * that u8 image.  Three launches: the tables (computed on the device, in
+ * double), the horizontal pass, the vertical pass.
+ * desc_host / desc_dev: the same nimg descriptors in host and in device memory
+ * (the caller uploads them; desc_dev 8-byte aligned).  The entry reads
+ * desc_host only, before any device call: QCN_ERR_ARG for a null pointer,
+ * nimg < 0, a non-positive size, a negative offset, a window outside
+ * (oh, ow), an image that runs past src_bytes or a workspace that is not
+ * 16-byte aligned; QCN_ERR_UNSUPPORTED when ceil(in / out) > 32 on either axis
+ * (more than 65 taps).  nimg == 0 launches nothing.
+ * workspace: qcn_resize_crop_workspace_size(...) bytes of device memory (host
+ * arithmetic; a negative status for a bad descriptor), no initialisation
+ * needed; concurrent streams need their own.  It starts with the tables: with
+ * S = qcn_resize_crop_tap_stride(...), the int32 record of column j of image
+ * i is at index (i * (cw + ch) + j) * S and that of row r at
+ * (i * (cw + ch) + cw + r) * S; a record is xmin, the tap count n, then
+ * k[0 .. n).  The u8 intermediate image follows the tables. */
+typedef struct qcn_resize_img_t {
+  long long offset;
+  int32_t h, w, oh, ow, top, left;
+} qcn_resize_img_t;
+long long qcn_resize_crop_workspace_size(const qcn_resize_img_t* desc_host, int nimg, int ch, int cw);
+int qcn_resize_crop_tap_stride(const qcn_resize_img_t* desc_host, int nimg, int ch, int cw);
+int qcn_resize_crop_u8_hwc(const uint8_t* src, long long src_bytes,
+                           const qcn_resize_img_t* desc_host, const qcn_resize_img_t* desc_dev,
+                           int nimg, int ch, int cw, uint8_t* y, void* workspace, void* stream);
+
 /* Inference BatchNorm1d (+ReLU) on fp32 [rows, cols] (bn7 of the reference's
  * StaticPTQModel between its dynamic fc1 and fc2, models/static_ptq_model.py:
  * 19-34 over baseline_model.py:80-82): y = fma(x, alpha[c], beta[c]), then
