@@ -25,6 +25,7 @@
 //    quadrants of the same 32 pooled pixels, so pooling is a register max.
 #include "common.hpp"
 #include "conv_epi.hpp"
+#include "conv_launch.hpp"
 #include <type_traits>
 #include <utility>
 #include <algorithm>
@@ -2665,12 +2666,60 @@ void convnet_convs_sm_kernel(const float* __restrict__ x, int nimg, float in_inv
 #endif
   C16_STAMP(3);
 }
+
+// the one-launch kernels of the fp32 input (convnet_convs below)
+struct ConvsF32 {
+  static constexpr auto sm = convnet_convs_sm_kernel;
+  template <int EM, bool KMAJOR>
+  static constexpr auto k16 = convnet_convs16_kernel<EM, KMAJOR>;
+  static constexpr int kLdsSm = kConvnetSmLds, kLds16 = kConvnet16Lds;
+};
 #endif  // QCN_CONV_U8_TU
 
 // Validates the six layers and picks the one-launch form for both input
 // kinds (definition and description with the C ABI below).
 int convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer_t* layers, int kmajor,
                        ConvnetLayers& L, int& em, int& ncu);
+
+// Host bodies of the entries that exist once per input kind (fp32 NCHW here,
+// raw u8 NHWC in conv3x3_u8.hip).  x and in are the kernel's first and third
+// arguments: the images, and 1 / in_scale or the QuantStub table.
+
+// conv1+conv2 by kernel K (persistent: one workgroup per CU); l1.x_zp is the
+// input zero point
+template <auto K, int LDS, class X, class IN>
+int conv12_fused(const X* x, int nimg, IN in, const qcn_conv_layer_t& l1, const qcn_conv_layer_t& l2, uint8_t* y,
+                 void* stream) {
+  if (!x || !y || nimg <= 0 || !layer_ok(l1) || !layer_ok(l2)) return QCN_ERR_ARG;
+  const ConvEpi ep1 = make_epi(l1), ep2 = make_epi(l2);
+  const int ncu = qcn_cu_count();
+  if (ncu <= 0) return QCN_ERR_HIP;
+  return launch_lds<K>(dim3(nimg < ncu ? nimg : ncu), dim3(512), LDS, (hipStream_t)stream, x, nimg, in,
+                       l1.x_zp, l1.w, ep1, l2.x_zp, l2.w, ep2, y);
+}
+
+// conv1 .. conv6 in one launch in the form convnet_convs_plan picks.  F names
+// the kernels of the input kind: F::sm (one image per workgroup, F::kLdsSm),
+// F::k16<EM, KMAJOR> (persistent, F::kLds16).
+template <class F, class X, class IN>
+int convnet_convs(const X* x, int nimg, IN in, float in_scale, int in_zp, const qcn_conv_layer_t* layers,
+                  uint8_t* a2, uint8_t* a4, uint8_t* a6, int kmajor, void* stream) {
+  if (!x || !layers || !a2 || !a4 || !a6) return QCN_ERR_ARG;
+  ConvnetLayers L;
+  int em = 0, ncu = 0;
+  const int form = convnet_convs_plan(nimg, in_scale, in_zp, layers, kmajor, L, em, ncu);
+  if (form < 0) return form;
+  hipStream_t st = (hipStream_t)stream;
+  if (form == 1)
+    return launch_lds<F::sm>(dim3(nimg), dim3(512), F::kLdsSm, st, x, nimg, in, QCN_C16_ARGS(L), a2, a4, a6);
+#define QCN_C16(EM_, KM_)                                                                                \
+  if (em == EM_ && (kmajor != 0) == KM_)                                                                 \
+    return launch_lds<F::template k16<EM_, KM_>>(dim3(ncu), dim3(512), F::kLds16, st, x, nimg, in,       \
+                                                 QCN_C16_ARGS(L), a2, a4, a6);
+  QCN_C16(1, true) QCN_C16(1, false) QCN_C16(2, true) QCN_C16(2, false)
+#undef QCN_C16
+  return QCN_ERR_UNSUPPORTED;
+}
 
 #ifndef QCN_CONV_U8_TU
 // --------------------------------------------------------------------------
@@ -2819,110 +2868,98 @@ void set_qdq(ConvEpi& ep, const qcn_qdq_t* q) {
 namespace {
 using namespace qcn;
 
+// workgroups of C::PXB pixels over the batch
+template <class C>
+int pixel_grid(int nimg) {
+  return (int)(((long)nimg * C::IMG + C::PXB - 1) / C::PXB);
+}
+
 template <int CIN, int COUT, int HW, bool POOL, int WPX, int PSP = 16, int RPAD = 0,
           int SPAD = 0, bool SPLIT = false, int JT = 4, int RB = 0>
 int launch_conv(const uint8_t* x, int nimg, int x_zp, const int8_t* wpk, const ConvEpi& ep,
                 uint8_t* y, hipStream_t st) {
   using C = ConvCfg<CIN, COUT, HW, POOL, WPX, PSP, RPAD, SPAD, SPLIT, 2, JT, RB>;
-  const long pix = (long)nimg * C::IMG;
-  const int grid = (int)((pix + C::PXB - 1) / C::PXB);
-  auto k = conv3x3_u8s8_kernel<CIN, COUT, HW, POOL, WPX, PSP, RPAD, SPAD, SPLIT, JT, RB>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, C::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(C::NT), C::LDS, st, x, nimg, x_zp, wpk, ep, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  return launch_lds<conv3x3_u8s8_kernel<CIN, COUT, HW, POOL, WPX, PSP, RPAD, SPAD, SPLIT, JT, RB>>(
+      dim3(pixel_grid<C>(nimg)), dim3(C::NT), C::LDS, st, x, nimg, x_zp, wpk, ep, y);
+}
+
+// what every conv-pair kernel takes: conv A's input and layer, conv B's
+// input zero point and layer, B's pooled output
+struct PairArgs {
+  const uint8_t* x;
+  int nimg, x_zp;
+  const int8_t* wa;
+  ConvEpi epa;
+  int xb_zp;
+  const int8_t* wb;
+  ConvEpi epb;
+  uint8_t* y;
+};
+template <auto K>
+int launch_pair_kernel(int grid, int nt, int lds, const PairArgs& a, hipStream_t st) {
+  return launch_lds<K>(dim3(grid), dim3(nt), lds, st, a.x, a.nimg, a.x_zp, a.wa, a.epa, a.xb_zp, a.wb, a.epb,
+                       a.y);
 }
 
 template <class CA, class CB>
-int launch_pair(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa,
-                int xb_zp, const int8_t* wb, const ConvEpi& epb, uint8_t* y, hipStream_t st) {
-  using P = PairCfg<CA, CB>;
-  const long pix = (long)nimg * CA::IMG;
-  const int grid = (int)((pix + CA::PXB - 1) / CA::PXB);
-  auto k = convpair_kernel<CA, CB>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(CA::NT), P::LDS, st, x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+int launch_pair(const PairArgs& a, hipStream_t st) {
+  return launch_pair_kernel<convpair_kernel<CA, CB>>(pixel_grid<CA>(a.nimg), CA::NT, PairCfg<CA, CB>::LDS, a, st);
 }
 
 template <class CA, class CB, int D>
-int launch_pair_ga(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa,
-                   int xb_zp, const int8_t* wb, const ConvEpi& epb, uint8_t* y, hipStream_t st) {
-  using P = PairGaCfg<CA, CB>;
-  const long pix = (long)nimg * CA::IMG;
-  const int grid = (int)((pix + CA::PXB - 1) / CA::PXB);
-  auto k = convpair_ga_kernel<CA, CB, D>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(CA::NT), P::LDS, st, x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+int launch_pair_ga(const PairArgs& a, hipStream_t st) {
+  return launch_pair_kernel<convpair_ga_kernel<CA, CB, D>>(pixel_grid<CA>(a.nimg), CA::NT,
+                                                           PairGaCfg<CA, CB>::LDS, a, st);
+}
+
+template <class CA, class CB, int D, int COUTB>
+int launch_pair_ga_split(const PairArgs& a, hipStream_t st) {
+  return launch_pair_kernel<convpair_ga_split_kernel<CA, CB, D, COUTB>>(
+      pixel_grid<CA>(a.nimg) * (COUTB / CB::kCout), CA::NT, PairGaCfg<CA, CB>::LDS, a, st);
+}
+
+// persistent: one workgroup per CU over tiles of P::SEGS images
+template <class P>
+int tile_grid(int nimg, int ncu) {
+  const int ntile = (nimg + P::SEGS - 1) / P::SEGS;
+  return ntile < ncu ? ntile : ncu;
 }
 
 template <class CA, class CB, int D, int FA, int FB, bool KM>
-int launch_pair_ws_k(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa, int xb_zp,
-                     const int8_t* wb, const ConvEpi& epb, uint8_t* y, hipStream_t st, int ncu) {
+int launch_pair_ws_k(const PairArgs& a, hipStream_t st, int ncu) {
   using P = PairWs<CA, CB, D>;
-  auto k = convpair_ws_kernel<CA, CB, D, FA, FB, KM>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  const int ntile = (nimg + P::SEGS - 1) / P::SEGS;
-  const int grid = ntile < ncu ? ntile : ncu;   // persistent: one workgroup per CU
-  hipLaunchKernelGGL(k, dim3(grid), dim3(512), P::LDS, st, x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  return launch_pair_kernel<convpair_ws_kernel<CA, CB, D, FA, FB, KM>>(tile_grid<P>(a.nimg, ncu), 512, P::LDS, a, st);
 }
 
 template <class CA, class CB, int FA, int FB, bool KM>
-int launch_pair_ws16_k(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa, int xb_zp,
-                       const int8_t* wb, const ConvEpi& epb, uint8_t* y, hipStream_t st, int ncu) {
+int launch_pair_ws16_k(const PairArgs& a, hipStream_t st, int ncu) {
   using P = PairWs16<CA, CB>;
-  auto k = convpair_ws16_kernel<CA, CB, FA, FB, KM>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  const int ntile = (nimg + P::SEGS - 1) / P::SEGS;
-  const int grid = ntile < ncu ? ntile : ncu;   // persistent: one workgroup per CU
-  hipLaunchKernelGGL(k, dim3(grid), dim3(512), P::LDS, st, x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  return launch_pair_kernel<convpair_ws16_kernel<CA, CB, FA, FB, KM>>(tile_grid<P>(a.nimg, ncu), 512, P::LDS, a, st);
 }
 
 template <class CA, class CB, int D, class CA16 = void, class CB16 = void>
-int launch_pair_ws(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa, int xb_zp,
-                   const int8_t* wb, const ConvEpi& epb, bool kmajor, uint8_t* y, hipStream_t st, int ncu) {
+int launch_pair_ws(const PairArgs& a, hipStream_t st, int ncu) {
   // epilogue modes, known on the host: 1 the FBGEMM fast path (zp_y == 0, no
   // floor, no QDQ hand-off), 2 the one-fma QDQ form (both convs: the QDQ
   // net), 0 general
-  int fa = epi_mode(epa), fb = epi_mode(epb);
+  int fa = epi_mode(a.epa), fb = epi_mode(a.epb);
   if ((fa == 2) != (fb == 2)) { fa = fa == 2 ? 0 : fa; fb = fb == 2 ? 0 : fb; }
+  const bool kmajor = a.epb.kmajor != 0;
   // the 16x16 forms for the two epilogue pairs the nets use (both convs on
   // the FBGEMM fast path, or both on the one-fma QDQ form); mixed forms stay
   // on the 32x32 kernel (results are identical: exact integer arithmetic)
   if constexpr (!std::is_void_v<CA16>) {
-#define QCN_WS16(FA_, FB_, KM_)                                                                      \
-  if (fa == FA_ && fb == FB_ && kmajor == KM_)                                                       \
-    return launch_pair_ws16_k<CA16, CB16, FA_, FB_, KM_>(x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y, st, ncu);
+#define QCN_WS16(FA_, FB_, KM_) \
+  if (fa == FA_ && fb == FB_ && kmajor == KM_) return launch_pair_ws16_k<CA16, CB16, FA_, FB_, KM_>(a, st, ncu);
     QCN_WS16(1, 1, false) QCN_WS16(2, 2, false) QCN_WS16(1, 1, true) QCN_WS16(2, 2, true)
 #undef QCN_WS16
   }
 #define QCN_WS(FA_, FB_, KM_) \
-  if (fa == FA_ && fb == FB_ && kmajor == KM_)                                                            \
-    return launch_pair_ws_k<CA, CB, D, FA_, FB_, KM_>(x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y, st, ncu);
+  if (fa == FA_ && fb == FB_ && kmajor == KM_) return launch_pair_ws_k<CA, CB, D, FA_, FB_, KM_>(a, st, ncu);
   QCN_WS(1, 1, false) QCN_WS(1, 0, false) QCN_WS(0, 1, false) QCN_WS(0, 0, false) QCN_WS(2, 2, false)
   QCN_WS(1, 1, true) QCN_WS(1, 0, true) QCN_WS(0, 1, true) QCN_WS(0, 0, true) QCN_WS(2, 2, true)
 #undef QCN_WS
   return QCN_ERR_UNSUPPORTED;
-}
-
-template <class CA, class CB, int D, int COUTB>
-int launch_pair_ga_split(const uint8_t* x, int nimg, int x_zp, const int8_t* wa, const ConvEpi& epa,
-                         int xb_zp, const int8_t* wb, const ConvEpi& epb, uint8_t* y, hipStream_t st) {
-  using P = PairGaCfg<CA, CB>;
-  const long pix = (long)nimg * CA::IMG;
-  const int grid = (int)((pix + CA::PXB - 1) / CA::PXB) * (COUTB / CB::kCout);
-  auto k = convpair_ga_split_kernel<CA, CB, D, COUTB>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(CA::NT), P::LDS, st, x, nimg, x_zp, wa, epa, xb_zp, wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 
 // Tuned instantiations: the SimpleConvNet layers and the
@@ -3039,20 +3076,13 @@ int qcn_conv3x3_pair_u8s8(const uint8_t* x, int nimg, int hw, int cin, int x_zp,
   if (!x || !wa_packed || !ua || !va || !multa || !corra || !wb_packed || !ub || !vb || !multb ||
       !corrb || !y)
     return QCN_ERR_ARG;
-  if (nimg <= 0 || hw <= 0 || x_zp < 0 || x_zp > 255 || zmid < 0 || zmid > 255 || y_zp < 0 ||
-      y_zp > 255)
-    return QCN_ERR_ARG;
-  ConvEpi epa{ua, va, multa, corra, zmid, relua ? zmid : 0, 0, 0.f, 0, 0.f, 0, 0};
-  int xb_zp = zmid;
-  if (qdqa) {
-    qcn::set_qdq(epa, qdqa);
-    xb_zp = qdqa->z2;
-  }
-  if (kmajor && (long)nimg * 4096 > 0x7fffffffL) return QCN_ERR_UNSUPPORTED;   // 32-bit store offsets
-  ConvEpi epb{ub, vb, multb, corrb, y_zp, relub ? y_zp : 0, 0, 0.f, 0, 0.f, 0, kmajor ? 1 : 0};
-  if (qdqb) qcn::set_qdq(epb, qdqb);
+  if (nimg <= 0 || hw <= 0 || !zp_ok(x_zp) || !zp_ok(zmid) || !zp_ok(y_zp)) return QCN_ERR_ARG;
+  if (kmajor && !offsets_fit(nimg)) return QCN_ERR_UNSUPPORTED;
+  // conv B reads conv A's output, or what A's QDQ hand-off makes of it
+  const PairArgs a{x, nimg, x_zp, wa_packed, make_epi(ua, va, multa, corra, zmid, relua, qdqa),
+                   qdqa ? qdqa->z2 : zmid, wb_packed, make_epi(ub, vb, multb, corrb, y_zp, relub, qdqb, kmajor),
+                   y};
   hipStream_t st = (hipStream_t)stream;
-  using namespace qcn;
   // wave tile: 64 couts x 128 pixels, two waves per SIMD (two workgroups per
   // CU for conv3+conv4).  ConvCfg's WI = 4 (128 x 128 tiles, one wave per
   // SIMD, a third fewer LDS bytes per MFMA) measured slower with no partner
@@ -3064,15 +3094,13 @@ int qcn_conv3x3_pair_u8s8(const uint8_t* x, int nimg, int hw, int cin, int x_zp,
     // 64-cout x 64-pixel wave tiles, conv4 as 32-cout x 128-pixel tiles — so
     // each SIMD holds two waves of the image's work instead of one
     if (nimg <= ncu)
-      return launch_pair<SmA3, SmB4>(
-          x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+      return launch_pair<SmA3, SmB4>(a, st);
     using A3 = WsA3;
     using B4 = WsB4;
     // two or more images per CU: the persistent wave-specialised kernel
     if (nimg >= 2 * ncu)
-      return launch_pair_ws<A3, B4, kPipeD, W16A3, W16B4>(x, nimg, x_zp, wa_packed, epa, xb_zp,
-                                                          wb_packed, epb, kmajor != 0, y, st, ncu);
-    return launch_pair<A3, B4>(x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+      return launch_pair_ws<A3, B4, kPipeD, W16A3, W16B4>(a, st, ncu);
+    return launch_pair<A3, B4>(a, st);
   }
   if (hw == 8 && cin == 128 && cmid == 256 && cout == 256) {
     // two images per 4-wave workgroup, two workgroups per CU, weights from L2
@@ -3083,13 +3111,11 @@ int qcn_conv3x3_pair_u8s8(const uint8_t* x, int nimg, int hw, int cin, int x_zp,
     // each computing all of conv5 (4/3 of the MFMAs, half the weight bytes per
     // image)
     if (nimg <= ncu)
-      return launch_pair_ga_split<A1, ConvCfg<256, 128, 8, true, 1, 16, 32, 64, true, 1>, 4, 256>(
-          x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+      return launch_pair_ga_split<A1, ConvCfg<256, 128, 8, true, 1, 16, 32, 64, true, 1>, 4, 256>(a, st);
     // two or more image pairs per CU: the persistent wave-specialised kernel
     if (nimg >= 4 * ncu)
-      return launch_pair_ws<A1, B1, kPipeD, W16A5, W16B6>(x, nimg, x_zp, wa_packed, epa, xb_zp,
-                                                          wb_packed, epb, kmajor != 0, y, st, ncu);
-    return launch_pair_ga<A1, B1, 4>(x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+      return launch_pair_ws<A1, B1, kPipeD, W16A5, W16B6>(a, st, ncu);
+    return launch_pair_ga<A1, B1, 4>(a, st);
   }
   return QCN_ERR_UNSUPPORTED;
 }
@@ -3100,13 +3126,13 @@ int qcn_conv3x3_u8s8_kmajor(const uint8_t* x, int nimg, int h, int w, int cin, i
                             uint8_t* y, void* stream) {
   if (!x || !w_packed || !u || !v || !mult || !corr || !y) return QCN_ERR_ARG;
   if (nimg <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return QCN_ERR_ARG;
-  if (x_zp < 0 || x_zp > 255 || y_zp < 0 || y_zp > 255) return QCN_ERR_ARG;
+  if (!zp_ok(x_zp) || !zp_ok(y_zp)) return QCN_ERR_ARG;
   if (pool && ((h & 1) || (w & 1))) return QCN_ERR_ARG;
   // whole images per workgroup: the 8x8 -> 4x4 and 8x8 layers of the net
   if (!(h == 8 && w == 8 && cin % 64 == 0 && cout == 256)) return QCN_ERR_UNSUPPORTED;
-  if ((long)nimg * 4096 > 0x7fffffffL) return QCN_ERR_UNSUPPORTED;   // 32-bit store offsets
-  ConvEpi ep{u, v, mult, corr, y_zp, relu ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 1};
-  return dispatch_conv(cin, cout, h, pool, x, nimg, x_zp, w_packed, ep, y, (hipStream_t)stream);
+  if (!offsets_fit(nimg)) return QCN_ERR_UNSUPPORTED;
+  return dispatch_conv(cin, cout, h, pool, x, nimg, x_zp, w_packed,
+                       make_epi(u, v, mult, corr, y_zp, relu, nullptr, true), y, (hipStream_t)stream);
 }
 
 int qcn_conv3x3_u8s8_nhwc(const uint8_t* x, int nimg, int h, int w, int cin, int x_zp,
@@ -3115,10 +3141,9 @@ int qcn_conv3x3_u8s8_nhwc(const uint8_t* x, int nimg, int h, int w, int cin, int
                           const qcn_qdq_t* qdq, uint8_t* y, void* stream) {
   if (!x || !w_packed || !u || !v || !mult || !corr || !y) return QCN_ERR_ARG;
   if (nimg <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return QCN_ERR_ARG;
-  if (x_zp < 0 || x_zp > 255 || y_zp < 0 || y_zp > 255) return QCN_ERR_ARG;
+  if (!zp_ok(x_zp) || !zp_ok(y_zp)) return QCN_ERR_ARG;
   if (pool && ((h & 1) || (w & 1))) return QCN_ERR_ARG;
-  ConvEpi ep{u, v, mult, corr, y_zp, relu ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq) qcn::set_qdq(ep, qdq);
+  const ConvEpi ep = make_epi(u, v, mult, corr, y_zp, relu, qdq);
   hipStream_t st = (hipStream_t)stream;
   if (h == w && cin % 64 == 0 && cout % 64 == 0) {
     const int rc = dispatch_conv(cin, cout, h, pool, x, nimg, x_zp, w_packed, ep, y, st);
@@ -3139,32 +3164,10 @@ int qcn_conv12_fused_f32_nchw(const float* x, int nimg, float in_scale, int in_z
                               const float* u2, const float* v2, const float* mult2,
                               const int32_t* corr2, int y_zp, int relu2, const qcn_qdq_t* qdq2,
                               uint8_t* y, void* stream) {
-  if (!x || !w1_packed || !u1 || !v1 || !mult1 || !corr1 || !w2_packed || !u2 || !v2 || !mult2 ||
-      !corr2 || !y)
-    return QCN_ERR_ARG;
-  if (nimg <= 0 || in_zp < 0 || in_zp > 255 || !(in_scale > 0.f) || x2_zp < 0 || x2_zp > 255 ||
-      y_zp < 0 || y_zp > 255 || z1 < 0 || z1 > 255)
-    return QCN_ERR_ARG;
-  ConvEpi ep1{u1, v1, mult1, corr1, z1, relu1 ? z1 : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq1) qcn::set_qdq(ep1, qdq1);
-  ConvEpi ep2{u2, v2, mult2, corr2, y_zp, relu2 ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq2) qcn::set_qdq(ep2, qdq2);
-  static bool attr_done[QCN_MAX_DEV] = {};
-  static int ncu_dev[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)qcn::conv12p_kernel, qcn::Conv12P::LDS, attr_done))
-    return QCN_ERR_HIP;
-  const int dev = qcn_current_device();
-  int& ncu = ncu_dev[dev];
-  if (!ncu && (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-               ncu <= 0)) {
-    ncu = 0;
-    return QCN_ERR_HIP;
-  }
-  const int grid = nimg < ncu ? nimg : ncu;   // persistent: one workgroup per CU
-  hipLaunchKernelGGL(qcn::conv12p_kernel, dim3(grid), dim3(512), qcn::Conv12P::LDS,
-                     (hipStream_t)stream, x, nimg, 1.0f / in_scale, in_zp, w1_packed, ep1, x2_zp,
-                     w2_packed, ep2, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  if (!(in_scale > 0.f)) return QCN_ERR_ARG;
+  return qcn::conv12_fused<qcn::conv12p_kernel, qcn::Conv12P::LDS>(
+      x, nimg, 1.0f / in_scale, {w1_packed, u1, v1, mult1, corr1, in_zp, z1, relu1, qdq1},
+      {w2_packed, u2, v2, mult2, corr2, x2_zp, y_zp, relu2, qdq2}, y, stream);
 }
 
 }  // extern "C"
@@ -3175,38 +3178,23 @@ int qcn_conv12_fused_f32_nchw(const float* x, int nimg, float in_scale, int in_z
 // the error the launch returns.
 int qcn::convnet_convs_plan(int nimg, float in_scale, int in_zp, const qcn_conv_layer_t* layers, int kmajor,
                             qcn::ConvnetLayers& L, int& em, int& ncu) {
-  if (!layers) return QCN_ERR_ARG;
-  if (nimg <= 0 || in_zp < 0 || in_zp > 255 || !(in_scale > 0.f)) return QCN_ERR_ARG;
+  if (nimg <= 0 || !zp_ok(in_zp) || !(in_scale > 0.f)) return QCN_ERR_ARG;
   L = qcn::ConvnetLayers{};
+  const int form36 = conv_layers_epi(layers, 6, 2, kmajor != 0, L.ep);
+  if (form36 < 0) return form36;
   for (int i = 0; i < 6; ++i) {
-    const qcn_conv_layer_t& l = layers[i];
-    if (!l.w || !l.u || !l.v || !l.mult || !l.corr) return QCN_ERR_ARG;
-    if (l.x_zp < 0 || l.x_zp > 255 || l.y_zp < 0 || l.y_zp > 255) return QCN_ERR_ARG;
-    // conv i reads conv i-1's output: its input zero point is that layer's
-    // output zero point, or the z2 of that layer's QDQ hand-off
-    if (i > 0 && l.x_zp != (layers[i - 1].qdq ? layers[i - 1].qdq->z2 : layers[i - 1].y_zp)) return QCN_ERR_ARG;
-    L.w[i] = l.w;
-    L.ep[i] = qcn::ConvEpi{l.u, l.v, l.mult, l.corr, l.y_zp, l.relu ? l.y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-    if (l.qdq) qcn::set_qdq(L.ep[i], l.qdq);
-    L.x_zp[i] = l.x_zp;
+    L.w[i] = layers[i].w;
+    L.x_zp[i] = layers[i].x_zp;
   }
   if (L.x_zp[0] != in_zp) return QCN_ERR_ARG;
-  L.ep[5].kmajor = kmajor ? 1 : 0;
-  if ((long)nimg * 4096 > 0x7fffffffL) return QCN_ERR_UNSUPPORTED;   // 32-bit store offsets
+  if (!offsets_fit(nimg)) return QCN_ERR_UNSUPPORTED;
   ncu = qcn_cu_count();
   if (ncu <= 0) return QCN_ERR_HIP;
   if (nimg <= ncu) return 1;   // one image per workgroup
   // the two pair phases are the wave-specialised kernels of >= 4 images per CU;
   // conv3..conv6 all on the FBGEMM fast epilogue or all on the one-fma QDQ form
-  if (nimg < 4 * ncu) return QCN_ERR_UNSUPPORTED;
-  bool all1 = true, all2 = true;
-  for (int i = 2; i < 6; ++i) {
-    all1 = all1 && qcn::epi_mode(L.ep[i]) == 1;
-    all2 = all2 && qcn::epi_mode(L.ep[i]) == 2;
-  }
-  if (all1) em = 1;
-  else if (all2) em = 2;
-  else return QCN_ERR_UNSUPPORTED;
+  if (nimg < 4 * ncu || form36 == 0) return QCN_ERR_UNSUPPORTED;
+  em = form36;
   return 2;
 }
 
@@ -3221,37 +3209,8 @@ int qcn_convnet_convs_form(int nimg, float in_scale, int in_zp, const qcn_conv_l
 int qcn_convnet_convs_f32_nchw(const float* x, int nimg, float in_scale, int in_zp,
                                const qcn_conv_layer_t* layers, uint8_t* a2, uint8_t* a4, uint8_t* a6,
                                int kmajor, void* stream) {
-  if (!x || !layers || !a2 || !a4 || !a6) return QCN_ERR_ARG;
-  qcn::ConvnetLayers L;
-  int em = 0, ncu = 0;
-  const int form = convnet_convs_plan(nimg, in_scale, in_zp, layers, kmajor, L, em, ncu);
-  if (form < 0) return form;
-  const float inv = 1.0f / in_scale;
-  if (form == 1) {   // one image per workgroup
-    static bool sm_done[QCN_MAX_DEV] = {};
-    if (!qcn_set_lds_once((const void*)qcn::convnet_convs_sm_kernel, qcn::kConvnetSmLds, sm_done))
-      return QCN_ERR_HIP;
-    hipLaunchKernelGGL(qcn::convnet_convs_sm_kernel, dim3(nimg), dim3(512), qcn::kConvnetSmLds,
-                       (hipStream_t)stream, x, nimg, inv, QCN_C16_ARGS(L), a2, a4, a6);
-    return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
-  }
-  static bool attr_done[4][QCN_MAX_DEV] = {};
-#define QCN_C16_KERNEL qcn::convnet_convs16_kernel
-#define QCN_C16_LDS qcn::kConvnet16Lds
-#define QCN_C16(EM_, KM_)                                                                          \
-  if (em == EM_ && (kmajor != 0) == KM_) {                                                         \
-    auto k = QCN_C16_KERNEL<EM_, KM_>;                                                             \
-    if (!qcn_set_lds_once((const void*)k, QCN_C16_LDS, attr_done[(EM_ - 1) * 2 + KM_]))            \
-      return QCN_ERR_HIP;                                                                          \
-    hipLaunchKernelGGL(k, dim3(ncu), dim3(512), QCN_C16_LDS, (hipStream_t)stream, x, nimg, inv,    \
-                       QCN_C16_ARGS(L), a2, a4, a6);                                               \
-    return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;                                 \
-  }
-  QCN_C16(1, true) QCN_C16(1, false) QCN_C16(2, true) QCN_C16(2, false)
-#undef QCN_C16
-#undef QCN_C16_KERNEL
-#undef QCN_C16_LDS
-  return QCN_ERR_UNSUPPORTED;
+  return qcn::convnet_convs<qcn::ConvsF32>(x, nimg, 1.0f / in_scale, in_scale, in_zp, layers, a2, a4, a6, kmajor,
+                                           stream);
 }
 
 int qcn_conv1_f32_nchw(const float* x, int nimg, int hw, float in_scale, int in_zp,
@@ -3260,8 +3219,7 @@ int qcn_conv1_f32_nchw(const float* x, int nimg, int hw, float in_scale, int in_
                        uint8_t* q_in, void* stream) {
   if (!x || !w1_packed || !u || !v || !mult || !corr || !y) return QCN_ERR_ARG;
   if (nimg <= 0 || in_zp < 0 || in_zp > 255 || !(in_scale > 0.f)) return QCN_ERR_ARG;
-  ConvEpi ep{u, v, mult, corr, y_zp, relu ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq) qcn::set_qdq(ep, qdq);
+  const ConvEpi ep = make_epi(u, v, mult, corr, y_zp, relu, qdq);
   const float inv = 1.0f / in_scale;
   hipStream_t st = (hipStream_t)stream;
   const long pix = (long)nimg * hw * hw;

@@ -60,9 +60,15 @@ void convnet_convs_sm_u8_kernel(const uint8_t* __restrict__ img, int nimg,
   convpair_ga_body<SmA5, SmB6, kSm56D>(b, a4, nimg, z4, w4, e4, z5, w5, e5, a6);
 }
 
-}  // namespace qcn
+// the one-launch kernels of the raw-u8 input (convnet_convs)
+struct ConvsU8 {
+  static constexpr auto sm = convnet_convs_sm_u8_kernel;
+  template <int EM, bool KMAJOR>
+  static constexpr auto k16 = convnet_convs16_u8_kernel<EM, KMAJOR>;
+  static constexpr int kLdsSm = kConvnetSmLdsU8, kLds16 = kConvnet16LdsU8;
+};
 
-using qcn::ConvEpi;
+}  // namespace qcn
 
 extern "C" {
 
@@ -73,61 +79,19 @@ int qcn_conv12_fused_u8_nhwc(const uint8_t* img, int nimg, const uint8_t* qlut, 
                              const float* u2, const float* v2, const float* mult2,
                              const int32_t* corr2, int y_zp, int relu2, const qcn_qdq_t* qdq2,
                              uint8_t* y, void* stream) {
-  if (!img || !qlut || !w1_packed || !u1 || !v1 || !mult1 || !corr1 || !w2_packed || !u2 || !v2 ||
-      !mult2 || !corr2 || !y)
-    return QCN_ERR_ARG;
-  if (nimg <= 0 || in_zp < 0 || in_zp > 255 || x2_zp < 0 || x2_zp > 255 || y_zp < 0 || y_zp > 255 ||
-      z1 < 0 || z1 > 255)
-    return QCN_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(img) & 3) return QCN_ERR_ARG;   // the window rows are dword loads
-  ConvEpi ep1{u1, v1, mult1, corr1, z1, relu1 ? z1 : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq1) qcn::set_qdq(ep1, qdq1);
-  ConvEpi ep2{u2, v2, mult2, corr2, y_zp, relu2 ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq2) qcn::set_qdq(ep2, qdq2);
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)qcn::conv12p_u8_kernel, qcn::Conv12P::LDS_U8, attr_done))
-    return QCN_ERR_HIP;
-  const int ncu = qcn_cu_count();
-  if (ncu <= 0) return QCN_ERR_HIP;
-  const int grid = nimg < ncu ? nimg : ncu;   // persistent: one workgroup per CU
-  hipLaunchKernelGGL(qcn::conv12p_u8_kernel, dim3(grid), dim3(512), qcn::Conv12P::LDS_U8,
-                     (hipStream_t)stream, img, nimg, qlut, in_zp, w1_packed, ep1, x2_zp, w2_packed, ep2,
-                     y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  // the window rows are dword loads
+  if (!qlut || (reinterpret_cast<uintptr_t>(img) & 3)) return QCN_ERR_ARG;
+  return qcn::conv12_fused<qcn::conv12p_u8_kernel, qcn::Conv12P::LDS_U8>(
+      img, nimg, qlut, {w1_packed, u1, v1, mult1, corr1, in_zp, z1, relu1, qdq1},
+      {w2_packed, u2, v2, mult2, corr2, x2_zp, y_zp, relu2, qdq2}, y, stream);
 }
 
 int qcn_convnet_convs_u8_nhwc(const uint8_t* img, int nimg, const uint8_t* qlut, int in_zp,
                               const qcn_conv_layer_t* layers, uint8_t* a2, uint8_t* a4, uint8_t* a6,
                               int kmajor, void* stream) {
-  if (!img || !qlut || !layers || !a2 || !a4 || !a6) return QCN_ERR_ARG;
-  if (nimg <= 0 || in_zp < 0 || in_zp > 255) return QCN_ERR_ARG;
-  if (reinterpret_cast<uintptr_t>(img) & 3) return QCN_ERR_ARG;   // the window rows are dword loads
-  qcn::ConvnetLayers L;
-  int em = 0, ncu = 0;
+  if (!qlut || (reinterpret_cast<uintptr_t>(img) & 3)) return QCN_ERR_ARG;   // dword window loads
   // the plan does not depend on the input scale (the table carries it)
-  const int form = qcn::convnet_convs_plan(nimg, 1.0f, in_zp, layers, kmajor, L, em, ncu);
-  if (form < 0) return form;
-  if (form == 1) {   // one image per workgroup
-    static bool sm_done[QCN_MAX_DEV] = {};
-    if (!qcn_set_lds_once((const void*)qcn::convnet_convs_sm_u8_kernel, qcn::kConvnetSmLdsU8, sm_done))
-      return QCN_ERR_HIP;
-    hipLaunchKernelGGL(qcn::convnet_convs_sm_u8_kernel, dim3(nimg), dim3(512), qcn::kConvnetSmLdsU8,
-                       (hipStream_t)stream, img, nimg, qlut, QCN_C16_ARGS(L), a2, a4, a6);
-    return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
-  }
-  static bool attr_done[4][QCN_MAX_DEV] = {};
-#define QCN_C16(EM_, KM_)                                                                          \
-  if (em == EM_ && (kmajor != 0) == KM_) {                                                         \
-    auto k = qcn::convnet_convs16_u8_kernel<EM_, KM_>;                                             \
-    if (!qcn_set_lds_once((const void*)k, qcn::kConvnet16LdsU8, attr_done[(EM_ - 1) * 2 + KM_]))   \
-      return QCN_ERR_HIP;                                                                          \
-    hipLaunchKernelGGL(k, dim3(ncu), dim3(512), qcn::kConvnet16LdsU8, (hipStream_t)stream, img,    \
-                       nimg, qlut, QCN_C16_ARGS(L), a2, a4, a6);                                   \
-    return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;                                 \
-  }
-  QCN_C16(1, true) QCN_C16(1, false) QCN_C16(2, true) QCN_C16(2, false)
-#undef QCN_C16
-  return QCN_ERR_UNSUPPORTED;
+  return qcn::convnet_convs<qcn::ConvsU8>(img, nimg, qlut, 1.0f, in_zp, layers, a2, a4, a6, kmajor, stream);
 }
 
 }  // extern "C"

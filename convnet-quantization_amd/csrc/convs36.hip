@@ -39,6 +39,7 @@
 // positions here.
 #include "common.hpp"
 #include "conv_epi.hpp"
+#include "conv_launch.hpp"
 #include <type_traits>
 
 namespace qcn {
@@ -557,39 +558,19 @@ extern "C" int qcn_convs36_u8s8(const uint8_t* a2, int nimg, const qcn_conv_laye
   using namespace qcn;
   if (!a2 || !layers || !a4 || !a6 || nimg <= 0) return QCN_ERR_ARG;
   ConvEpi ep[4];
-  for (int i = 0; i < 4; ++i) {
-    const qcn_conv_layer_t& l = layers[i];
-    if (!l.w || !l.u || !l.v || !l.mult || !l.corr) return QCN_ERR_ARG;
-    if (l.x_zp < 0 || l.x_zp > 255 || l.y_zp < 0 || l.y_zp > 255) return QCN_ERR_ARG;
-    if (i > 0 && l.x_zp != (layers[i - 1].qdq ? layers[i - 1].qdq->z2 : layers[i - 1].y_zp)) return QCN_ERR_ARG;
-    ep[i] = ConvEpi{l.u, l.v, l.mult, l.corr, l.y_zp, l.relu ? l.y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-    if (l.qdq) set_qdq(ep[i], l.qdq);
-  }
-  ep[3].kmajor = kmajor ? 1 : 0;
-  if ((long)nimg * 4096 > 0x7fffffffL) return QCN_ERR_UNSUPPORTED;   // 32-bit store offsets
   // conv3 .. conv6 all on the FBGEMM fast epilogue, or all on the one-fma QDQ form
-  int em = 0;
-  bool all1 = true, all2 = true;
-  for (int i = 0; i < 4; ++i) {
-    all1 = all1 && epi_mode(ep[i]) == 1;
-    all2 = all2 && epi_mode(ep[i]) == 2;
-  }
-  if (all1) em = 1;
-  else if (all2) em = 2;
-  else return QCN_ERR_UNSUPPORTED;
+  const int em = conv_layers_epi(layers, 4, 0, kmajor != 0, ep);
+  if (em < 0) return em;
+  if (!offsets_fit(nimg) || em == 0) return QCN_ERR_UNSUPPORTED;
   const int ncu = qcn_cu_count();
   if (ncu <= 0) return QCN_ERR_HIP;
   const int grid = nimg < ncu ? nimg : ncu;   // persistent: one workgroup per CU
-  static bool attr_done[4][QCN_MAX_DEV] = {};
-#define QCN_W4(EM_, KM_)                                                                                \
-  if (em == EM_ && (kmajor != 0) == KM_) {                                                              \
-    auto k = convs36_w4_kernel<EM_, KM_>;                                                               \
-    if (!qcn_set_lds_once((const void*)k, kW4Lds, attr_done[(EM_ - 1) * 2 + KM_])) return QCN_ERR_HIP; \
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), kW4Lds, (hipStream_t)stream, a2, nimg, layers[0].w,     \
-                       ep[0], layers[0].x_zp, layers[1].w, ep[1], layers[1].x_zp, layers[2].w, ep[2],   \
-                       layers[2].x_zp, layers[3].w, ep[3], layers[3].x_zp, a4, a6);                     \
-    return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;                                      \
-  }
+#define QCN_W4(EM_, KM_)                                                                                 \
+  if (em == EM_ && (kmajor != 0) == KM_)                                                                 \
+    return launch_lds<convs36_w4_kernel<EM_, KM_>>(                                                      \
+        dim3(grid), dim3(256), kW4Lds, (hipStream_t)stream, a2, nimg, layers[0].w, ep[0], layers[0].x_zp, \
+        layers[1].w, ep[1], layers[1].x_zp, layers[2].w, ep[2], layers[2].x_zp, layers[3].w, ep[3],      \
+        layers[3].x_zp, a4, a6);
   QCN_W4(1, true) QCN_W4(1, false) QCN_W4(2, true) QCN_W4(2, false)
 #undef QCN_W4
   return QCN_ERR_UNSUPPORTED;

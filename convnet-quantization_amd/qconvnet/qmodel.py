@@ -320,8 +320,7 @@ class QuantizedConvNet:
         # one-wave-per-SIMD workgroups (qcn_convs36_u8s8, r06) instead of the
         # one-launch conv1 .. conv6 (fuse_convs), from 4 images per CU
         self.convs_w4 = False
-        self._w4_ok = {}         # batch size -> whether the conv3 .. conv6 launch ran
-        self._convs_ok = {}      # batch size -> whether the one-launch convs ran
+        self._plans = {}         # (input shape, keep, the five switches) -> launch plan
         self._conv_layers = None
         self._bufs = {}
         self._graphs = {}
@@ -405,24 +404,28 @@ class QuantizedConvNet:
             self._bufs[(n, slot)] = b
         return b
 
-    # --------------------------------------------------------------- forward
-    KERNELS = ("conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "fc1", "fc2")
-    KERNELS_FUSED = ("conv12", "conv3", "conv4", "conv5", "conv6", "fc1", "fc2")
+    def _lazy(self, b, name):
+        """A buffer only some plans use (conv6's chunk-major output, the
+        normalised fp32 copy of raw images, the head's workspace), made on
+        its first use in buffer set ``b``."""
+        t = b.get(name)
+        if t is None:
+            n = b["a2"].shape[0]
+            if name == "a6k":
+                t = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
+            elif name == "xf":
+                t = torch.empty((n, 3, 32, 32), dtype=torch.float32, device=self.device)
+            else:
+                t = ops.classifier_workspace(n, self.fc1.w.shape[0], self.device)
+            b[name] = t
+        return t
 
+    # --------------------------------------------------------------- forward
     def kernel_names(self, x_shape, keep=False):
         """Names of the launches run() marks, in order (conv1+conv2 are one
         launch when fused, conv3+conv4 / conv5+conv6 one launch each when
         paired, fc1+fc2 one "fc12" slot for the fused head)."""
-        if self._w4(x_shape, keep):
-            return ("conv12", "conv3_6", "fc12") if self._head(x_shape[0], keep) else ("conv12", "conv3_6", "fc1", "fc2")
-        if self._convs(x_shape, keep) and self._convs_form(x_shape[0], keep):
-            return ("conv1_6", "fc12") if self._head(x_shape[0], keep) else ("conv1_6", "fc1", "fc2")
-        names = list(self.KERNELS_FUSED if self._fused(x_shape) else self.KERNELS)
-        if self._pairs(keep):
-            names[names.index("conv3"):names.index("conv6") + 1] = ["conv34", "conv56"]
-        if self._head(x_shape[0], keep):
-            names = names[:-2] + ["fc12"]
-        return tuple(names)
+        return tuple(name for name, _ in self._plan(x_shape, keep))
 
     def _pairs(self, keep):
         """conv3+conv4 and conv5+conv6 as fused block launches (their middle
@@ -451,33 +454,135 @@ class QuantizedConvNet:
         # fp32 NCHW or raw u8 NHWC images
         return self.fuse12 and tuple(x_shape[1:]) in ((3, 32, 32), (32, 32, 3))
 
-    def _convs_form(self, n, keep=False):
-        """Whether the library takes the one-launch convs at batch n: what a
-        run() recorded, else the library's host query (no launch), so
-        kernel_names() is right before the first forward at a batch size."""
-        ok = self._convs_ok.get(n)
-        if ok is None:
-            if self._conv_layers is None:
-                self._conv_layers = ops.conv_layers(self.L, self.in_zp)
-            with torch.cuda.device(self.device):
-                ok = ops.convnet_convs_form(n, self.in_scale, self.in_zp, self._conv_layers,
-                                            kmajor=self._head(n, keep)) > 0
-        return ok
+    def _convs_form(self, n, head):
+        """The library's host query (no launch) for the one-launch convs at
+        batch n: 1 one image per workgroup, 2 persistent, 0 not taken."""
+        if self._conv_layers is None:
+            self._conv_layers = ops.conv_layers(self.L, self.in_zp)
+        with torch.cuda.device(self.device):
+            return ops.convnet_convs_form(n, self.in_scale, self.in_zp, self._conv_layers, kmajor=head)
 
-    def _w4(self, x_shape, keep):
-        """conv12 + the one-wave-per-SIMD conv3 .. conv6 launch applies: from 4
-        images per CU (below that its 4-image conv5+6 tiles are mostly empty),
-        unless the library declined this batch size before."""
-        n = x_shape[0]
-        if not (self.convs_w4 and self._fused(x_shape) and self._pairs(keep) and self._w4_ok.get(n, True)):
-            return False
-        ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
-        return n >= 4 * ncu
+    def _plan(self, x_shape, keep):
+        """The launch plan of a forward: a tuple of (name, step), one per
+        launch run() marks, each step a callable of (input, buffer set).
+        Built once per input shape, keep and switch setting (tests and tools
+        flip the switches between forwards), so a later forward asks the
+        library nothing."""
+        key = (tuple(x_shape), keep, self.fuse12, self.fuse_pairs, self.fc_head, self.fuse_convs, self.convs_w4)
+        plan = self._plans.get(key)
+        if plan is None:
+            plan = self._plans[key] = self._build_plan(key[0], keep)
+        return plan
 
-    def _convs(self, x_shape, keep):
-        """The one-launch conv1 .. conv6 applies to this forward (the library
-        may still decline the batch size: _convs_ok records that per size)."""
-        return self.fuse_convs and self._fused(x_shape) and self._pairs(keep)
+    def _build_plan(self, x_shape, keep):
+        n, L = x_shape[0], self.L
+        fused, pairs, head = self._fused(x_shape), self._pairs(keep), self._head(n, keep)
+        out6 = "a6k" if head else "a6"   # conv6 writes the head's chunk-major input
+        acts = ["a1", "a2", "a3", "a4", "a5", "a6"]
+        steps = []
+
+        def step(name):
+            def add(fn):
+                steps.append((name, fn))
+            return add
+
+        def must(ok, what):
+            if not ok:
+                raise RuntimeError(f"{what} rejected a launch the plan chose")
+
+        # the one-launch forms take what the library's plan function takes:
+        # form 1 (one image per workgroup) or 2 (persistent, all of conv3 ..
+        # conv6 on one epilogue form); the conv3 .. conv6 launch is form 2's
+        form = self._convs_form(n, head) if fused and pairs and (self.fuse_convs or self.convs_w4) else 0
+        w4 = self.convs_w4 and form == 2
+        if self.fuse_convs and form > 0 and not w4:
+            @step("conv1_6")
+            def _(x, b):
+                if x.dtype == torch.uint8:
+                    ok = ops.convnet_convs_u8(x, self.qlut, self.in_zp, self._conv_layers, b["a2"], b["a4"],
+                                              self._lazy(b, out6), kmajor=head)
+                else:
+                    ok = ops.convnet_convs(x, self.in_scale, self.in_zp, self._conv_layers, b["a2"], b["a4"],
+                                           self._lazy(b, out6), kmajor=head)
+                must(ok, "one-launch convs")
+            first = 6
+        elif fused:
+            @step("conv12")
+            def _(x, b):
+                if x.dtype == torch.uint8:
+                    ops.conv12_fused_u8(x, self.qlut, self.in_zp, L[0], L[1], out=b["a2"])
+                else:
+                    ops.conv12_fused(x, self.in_scale, self.in_zp, L[0], L[1], out=b["a2"])
+            first = 2
+        else:
+            @step("conv1")
+            def _(x, b):
+                d = L[0]
+                if x.dtype == torch.uint8:   # the stand-alone conv1 has no u8 stage: normalise first
+                    x = ops.normalize_u8(x, self.ntab, out=self._lazy(b, "xf"))
+                ops.conv1_f32(x, self.in_scale, self.in_zp, d.w, d.u, d.v, d.mult, d.corr, d.z_y, d.relu, d.qdq,
+                              out=b["a1"])
+            first = 1
+        if w4:
+            @step("conv3_6")
+            def _(x, b):
+                must(ops.convs36(b["a2"], self._conv_layers, b["a4"], self._lazy(b, out6), kmajor=head),
+                     "conv3 .. conv6 launch")
+            first = 6
+
+        def conv_pair(i, src, dst):   # conv3+conv4, conv5+conv6 in one launch each
+            @step(f"conv{i + 1}{i + 2}")
+            def _(x, b):
+                must(ops.conv_pair(b[src], L[i], L[i + 1], self._lazy(b, dst), kmajor=dst == "a6k"), "fused conv pair")
+
+        def conv(i, src, dst):
+            d = L[i]
+
+            @step(f"conv{i + 1}")
+            def _(x, b):
+                if dst == "a6k":   # conv6 writes the classifier's chunk-major input
+                    must(ops.conv3x3_kmajor(b[src], d.z_x, d.w, d.cout, d.u, d.v, d.mult, d.corr, d.z_y, d.relu,
+                                            d.pool, self._lazy(b, dst)), "chunk-major conv6")
+                else:
+                    ops.conv3x3(b[src], d.z_x, d.w, d.cout, d.u, d.v, d.mult, d.corr, d.z_y, d.relu, d.pool,
+                                d.qdq, out=b[dst])
+
+        i = first
+        while i < 6:   # L[i] is conv i+1: it reads acts[i - 1]
+            if pairs and i in (2, 4):
+                conv_pair(i, acts[i - 1], out6 if i == 4 else acts[i + 1])
+                i += 2
+            else:
+                conv(i, acts[i - 1], out6 if i == 5 else acts[i])
+                i += 1
+
+        f1, f2 = self.fc1, self.fc2
+        if head:
+            @step("fc12")
+            def _(x, b):
+                must(self._classifier(b["a6k"], b), "classifier head")
+                if keep:  # NHWC view of conv6's output for inspection / parity tests
+                    b["a6"].copy_(ops.from_kmajor(b["a6k"]).view(n, 4, 4, 256))
+        elif self.mode == "static":
+            @step("fc1")
+            def _(x, b):
+                ops.linear_u8(b["a6"].view(n, 4096), f1.z_x, f1.w, f1.u, f1.v, f1.mult, f1.corr, f1.z_y, True,
+                              out=b["f1"])
+
+            @step("fc2")
+            def _(x, b):
+                ops.linear_u8(b["f1"], f2.z_x, f2.w, f2.u, f2.v, f2.mult, f2.corr, f2.z_y, False,
+                              y_scale=f2.s_y, want_fp32=True, out=b["q"], out_f=b["logits"])
+        else:
+            @step("fc1")
+            def _(x, b):
+                ops.linear_u8(b["a6"].view(n, 4096), f1.z_x, f1.w, f1.u, f1.v, f1.mult, f1.corr, f1.z_y, False,
+                              y_scale=f1.s_y, want_fp32=True, out=b["f1"], out_f=b["f1f"])
+
+            @step("fc2")
+            def _(x, b):
+                ops.linear_f32(b["f1f"], f2.w, f2.b, relu_in=True, out=b["logits"])
+        return tuple(steps)
 
     def run(self, x, keep=False, marks=None, slot=0):
         """Launch the whole int8 forward on the current stream of the model's
@@ -496,9 +601,7 @@ class QuantizedConvNet:
             return self._run(x, keep, marks, slot)
 
     def _run(self, x, keep, marks, slot=0):
-        n = x.shape[0]
-        b = self._buffers(n, slot)
-        L = self.L
+        b = self._buffers(x.shape[0], slot)
 
         def mark():
             if marks is not None:
@@ -507,114 +610,9 @@ class QuantizedConvNet:
                 marks.append(ev)
 
         mark()
-        d = L[0]
-        names = ["a2", "a3", "a4", "a5", "a6"]
-        u8 = x.dtype == torch.uint8
-
-        def conv12():
-            if u8:
-                ops.conv12_fused_u8(x, self.qlut, self.in_zp, L[0], L[1], out=b["a2"])
-            else:
-                ops.conv12_fused(x, self.in_scale, self.in_zp, L[0], L[1], out=b["a2"])
-
-        head = self._head(n, keep)
-        convs_done = conv12_done = False
-        if self._w4(x.shape, keep):
-            if self._conv_layers is None:
-                self._conv_layers = ops.conv_layers(L, self.in_zp)
-            conv12()
+        for _, step in self._plan(x.shape, keep):
+            step(x, b)
             mark()
-            if head and "a6k" not in b:
-                b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
-            out6 = b["a6k"] if head else b["a6"]
-            w4_done = ops.convs36(b["a2"], self._conv_layers, b["a4"], out6, kmajor=head)
-            self._w4_ok[n] = w4_done
-            if w4_done:
-                mark()
-                prev, first, convs_done = b["a6"], 6, True
-            else:   # (mixed epilogue forms) the pair launches from a2
-                prev, first, conv12_done = b["a2"], 2, True
-        elif self._convs(x.shape, keep) and self._convs_ok.get(n, True):
-            if head and "a6k" not in b:
-                b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
-            if self._conv_layers is None:
-                self._conv_layers = ops.conv_layers(L, self.in_zp)
-            out6 = b["a6k"] if head else b["a6"]
-            if u8:
-                convs_done = ops.convnet_convs_u8(x, self.qlut, self.in_zp, self._conv_layers, b["a2"],
-                                                  b["a4"], out6, kmajor=head)
-            else:
-                convs_done = ops.convnet_convs(x, self.in_scale, self.in_zp, self._conv_layers, b["a2"],
-                                               b["a4"], out6, kmajor=head)
-            self._convs_ok[n] = convs_done
-            if convs_done:
-                mark()
-                prev, first = b["a6"], 6
-        if convs_done or conv12_done:
-            pass
-        elif self._fused(x.shape):
-            conv12()
-            mark()
-            prev, first = b["a2"], 2
-        else:
-            if u8:   # the stand-alone conv1 has no u8 stage: normalise first
-                if "xf" not in b:
-                    b["xf"] = torch.empty((n, 3, 32, 32), dtype=torch.float32, device=self.device)
-                x = ops.normalize_u8(x, self.ntab, out=b["xf"])
-            ops.conv1_f32(x, self.in_scale, self.in_zp, d.w, d.u, d.v, d.mult, d.corr, d.z_y,
-                          d.relu, d.qdq, out=b["a1"])
-            mark()
-            prev, first = b["a1"], 1
-        pairs = self._pairs(keep)
-        for i in range(first, 6):
-            d = L[i]
-            if pairs and i in (2, 4):   # conv3+conv4, conv5+conv6 in one launch each
-                nb = L[i + 1]
-                if i == 4 and head:
-                    if "a6k" not in b:
-                        b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
-                    out, km = b["a6k"], True
-                else:
-                    out, km = b[names[i]], False
-                if not ops.conv_pair(prev, d, nb, out, kmajor=km):
-                    raise RuntimeError("fused conv pair rejected a supported shape")
-                mark()
-                prev = out
-                continue
-            if pairs and i in (3, 5):
-                continue
-            if i == 5 and head:   # conv6 writes the classifier's chunk-major input
-                if "a6k" not in b:
-                    b["a6k"] = torch.empty((128, n, 32), dtype=torch.uint8, device=self.device)
-                if not ops.conv3x3_kmajor(prev, d.z_x, d.w, d.cout, d.u, d.v, d.mult, d.corr,
-                                          d.z_y, d.relu, d.pool, b["a6k"]):
-                    raise RuntimeError("chunk-major conv6 rejected a supported shape")
-                mark()
-                continue
-            ops.conv3x3(prev, d.z_x, d.w, d.cout, d.u, d.v, d.mult, d.corr, d.z_y, d.relu, d.pool,
-                        d.qdq, out=b[names[i - 1]])
-            mark()
-            prev = b[names[i - 1]]
-        f1, f2 = self.fc1, self.fc2
-        if head:
-            if not self._classifier(b["a6k"], b):
-                raise RuntimeError("classifier head rejected a supported shape")
-            if keep:  # NHWC view of conv6's output for inspection / parity tests
-                b["a6"].copy_(ops.from_kmajor(b["a6k"]).view(n, 4, 4, 256))
-        elif self.mode == "static":
-            flat = prev.view(n, 4096)
-            ops.linear_u8(flat, f1.z_x, f1.w, f1.u, f1.v, f1.mult, f1.corr, f1.z_y, True,
-                          out=b["f1"])
-            mark()
-            ops.linear_u8(b["f1"], f2.z_x, f2.w, f2.u, f2.v, f2.mult, f2.corr, f2.z_y, False,
-                          y_scale=f2.s_y, want_fp32=True, out=b["q"], out_f=b["logits"])
-        else:
-            flat = prev.view(n, 4096)
-            ops.linear_u8(flat, f1.z_x, f1.w, f1.u, f1.v, f1.mult, f1.corr, f1.z_y, False,
-                          y_scale=f1.s_y, want_fp32=True, out=b["f1"], out_f=b["f1f"])
-            mark()
-            ops.linear_f32(b["f1f"], f2.w, f2.b, relu_in=True, out=b["logits"])
-        mark()
         if keep:
             return b["logits"], b
         return b["logits"]
@@ -624,13 +622,11 @@ class QuantizedConvNet:
         chunk-major conv6 output + a per-row finisher); in QDQ mode fc1's
         dequantize, ReLU and the fp32 fc2 run in the finisher."""
         f1, f2 = self.fc1, self.fc2
-        n = xk.shape[1]
-        if "ws" not in b:
-            b["ws"] = ops.classifier_workspace(n, f1.w.shape[0], self.device)
+        ws = self._lazy(b, "ws")
         if self.mode == "qdq":
-            return ops.classifier_qdq(xk, f1, f2, b["ws"], b["f1"], b["logits"])
+            return ops.classifier_qdq(xk, f1, f2, ws, b["f1"], b["logits"])
         f1.relu, f2.relu = True, False
-        return ops.classifier(xk, f1, f2, b["ws"], b["f1"], b["q"], b["logits"])
+        return ops.classifier(xk, f1, f2, ws, b["f1"], b["q"], b["logits"])
 
     def run_pipelined(self, batches, streams):
         """Forward a sequence of batches with len(streams) of them in flight:

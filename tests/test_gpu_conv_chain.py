@@ -94,9 +94,11 @@ def _run(model, x, path):
             t.fill_(0xA5) if t.dtype == torch.uint8 else t.zero_()
     except KeyError:
         pass
-    model.run(x, keep=keep)
+    marks = []
+    model.run(x, keep=keep, marks=marks)
     torch.cuda.synchronize()
     names = model.kernel_names(x.shape, keep=keep)
+    assert len(marks) == len(names) + 1   # one event before the first launch, one after each
     b = model.buffers(n)
     want = ("a1", "a2", "a3", "a4", "a5", "a6") if keep else ("a2", "a4", "a6")
     got = {k: b[k].clone() for k in want + ("f1", "logits")}
@@ -158,9 +160,9 @@ def test_fused_launches_equal_oracle(dev, cache, profile, size):
     runs, bad = {}, []
     for path in paths:
         want = _expect_names(profile, n, ncu, path)
-        model.fuse12, model.fuse_convs, model.convs_w4 = path != "layers", path in ("default", "w4"), False
-        if path != "w4":   # right before the first forward too (the host query)
-            assert model.kernel_names(x.shape, keep=path == "layers") == want, (path, "before the run")
+        model.fuse12, model.fuse_convs, model.convs_w4 = path != "layers", path in ("default", "w4"), path == "w4"
+        # right before the first forward too (the host query)
+        assert model.kernel_names(x.shape, keep=path == "layers") == want, (path, "before the run")
         names, got = _run(model, x, path)
         print(f"{profile} n={n} {path}: {' '.join(names)}")
         assert names == want, path

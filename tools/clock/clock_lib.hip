@@ -90,33 +90,11 @@ void conv12p_stamped(const float* __restrict__ x, int nimg, float in_inv, int in
 }
 
 namespace {
-template <class CA, class CB>
-int launch_pair_stamped(int kind, const uint8_t* x, int nimg, int x_zp, const int8_t* wa,
-                        const ConvEpi& epa, int xb_zp, const int8_t* wb, const ConvEpi& epb,
-                        uint8_t* y, hipStream_t st) {
-  using P = PairCfg<CA, CB>;
-  const long pix = (long)nimg * CA::IMG;
-  const int grid = (int)((pix + CA::PXB - 1) / CA::PXB);
-  auto k = convpair_stamped<CA, CB>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(CA::NT), P::LDS, st, kind, x, nimg, x_zp, wa, epa, xb_zp,
-                     wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
-}
-template <class CA, class CB, int D>
-int launch_pair_ga_stamped(int kind, const uint8_t* x, int nimg, int x_zp, const int8_t* wa,
-                           const ConvEpi& epa, int xb_zp, const int8_t* wb, const ConvEpi& epb,
-                           uint8_t* y, hipStream_t st) {
-  using P = PairGaCfg<CA, CB>;
-  const long pix = (long)nimg * CA::IMG;
-  const int grid = (int)((pix + CA::PXB - 1) / CA::PXB);
-  auto k = convpair_ga_stamped<CA, CB, D>;
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-  hipLaunchKernelGGL(k, dim3(grid), dim3(CA::NT), P::LDS, st, kind, x, nimg, x_zp, wa, epa, xb_zp,
-                     wb, epb, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+// the stamped kernels take the stamp slot (kind) before the pair's arguments
+template <auto K>
+int launch_stamped(int kind, int grid, int nt, int lds, const PairArgs& a, hipStream_t st) {
+  return launch_lds<K>(dim3(grid), dim3(nt), lds, st, kind, a.x, a.nimg, a.x_zp, a.wa, a.epa, a.xb_zp, a.wb,
+                       a.epb, a.y);
 }
 }  // namespace
 }  // namespace qcn
@@ -134,18 +112,9 @@ int qcn_conv3x3_pair_u8s8(const uint8_t* x, int nimg, int hw, int cin, int x_zp,
                           const float* vb, const float* multb, const int32_t* corrb, int y_zp,
                           int relub, const qcn_qdq_t* qdqb, int kmajor, uint8_t* y, void* stream) {
   using namespace qcn;
-  ConvEpi epa{ua, va, multa, corra, zmid, relua ? zmid : 0, 0, 0.f, 0, 0.f, 0, 0};
-  int xb_zp = zmid;
-  if (qdqa) {
-    epa.qdq = 1;
-    epa.s1 = qdqa->s1; epa.z1 = qdqa->z1; epa.inv2 = qdqa->inv2; epa.z2 = qdqa->z2;
-    xb_zp = qdqa->z2;
-  }
-  ConvEpi epb{ub, vb, multb, corrb, y_zp, relub ? y_zp : 0, 0, 0.f, 0, 0.f, 0, kmajor ? 1 : 0};
-  if (qdqb) {
-    epb.qdq = 1;
-    epb.s1 = qdqb->s1; epb.z1 = qdqb->z1; epb.inv2 = qdqb->inv2; epb.z2 = qdqb->z2;
-  }
+  const PairArgs a{x, nimg, x_zp, wa_packed, make_epi(ua, va, multa, corra, zmid, relua, qdqa),
+                   qdqa ? qdqa->z2 : zmid, wb_packed, make_epi(ub, vb, multb, corrb, y_zp, relub, qdqb, kmajor),
+                   y};
   hipStream_t st = (hipStream_t)stream;
   // the product's default forms (qcn_conv3x3_pair_u8s8): at <= 1 image per
   // CU conv3+4 on eight waves per image and the cout-split conv5+6
@@ -154,33 +123,22 @@ int qcn_conv3x3_pair_u8s8(const uint8_t* x, int nimg, int hw, int cin, int x_zp,
   if (hw == 16 && cin == 64 && cmid == 128 && cout == 128) {
     g_last34_ws = nimg >= 2 * ncu;
     if (small)
-      return launch_pair_stamped<ConvCfg<64, 128, 16, false, 4, 16, 96, 0, false, 2, 2>,
-                                 ConvCfg<128, 128, 16, true, 2, 16, 32, 0, true, 1, 4>>(
-          1, x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+      return launch_stamped<convpair_stamped<SmA3, SmB4>>(1, pixel_grid<SmA3>(nimg), SmA3::NT,
+                                                          PairCfg<SmA3, SmB4>::LDS, a, st);
     // the product's wave-specialised kernel, built here with its stamps
-    return launch_pair_ws<ConvCfg<64, 128, 16, false, 2, 16, 96, 0, false>,
-                          ConvCfg<128, 128, 16, true, 2, 16, 32, 0, true>, kPipeD>(
-        x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, kmajor != 0, y, st, ncu);
+    return launch_pair_ws<WsA3, WsB4, kPipeD>(a, st, ncu);
   }
   if (hw == 8 && cin == 128 && cmid == 256 && cout == 256) {
-    using A1 = ConvCfg<128, 256, 8, false, 1, 16, 224, 0, false>;
+    using A1 = WsA5;
     if (small) {
       using BS = ConvCfg<256, 128, 8, true, 1, 16, 32, 64, true, 1>;
-      using P = PairGaCfg<A1, BS>;
-      const int grid = (int)(((long)nimg * A1::IMG + A1::PXB - 1) / A1::PXB) * 2;
-      auto k = convpair_ga_split_stamped<A1, BS, 4, 256>;
-      static bool attr_done[QCN_MAX_DEV] = {};
-      if (!qcn_set_lds_once((const void*)k, P::LDS, attr_done)) return QCN_ERR_HIP;
-      hipLaunchKernelGGL(k, dim3(grid), dim3(A1::NT), P::LDS, st, 2, x, nimg, x_zp, wa_packed, epa,
-                         xb_zp, wb_packed, epb, y);
-      return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+      return launch_stamped<convpair_ga_split_stamped<A1, BS, 4, 256>>(2, pixel_grid<A1>(nimg) * 2, A1::NT,
+                                                                       PairGaCfg<A1, BS>::LDS, a, st);
     }
-    using B1 = ConvCfg<256, 256, 8, true, 1, 16, 32, 64, true>;
     g_last56_ws = nimg >= 4 * ncu;
-    if (g_last56_ws)
-      return launch_pair_ws<A1, B1, kPipeD>(x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb,
-                                                  kmajor != 0, y, st, ncu);
-    return launch_pair_ga_stamped<A1, B1, 4>(2, x, nimg, x_zp, wa_packed, epa, xb_zp, wb_packed, epb, y, st);
+    if (g_last56_ws) return launch_pair_ws<A1, WsB6, kPipeD>(a, st, ncu);
+    return launch_stamped<convpair_ga_stamped<A1, WsB6, 4>>(2, pixel_grid<A1>(nimg), A1::NT,
+                                                            PairGaCfg<A1, WsB6>::LDS, a, st);
   }
   return QCN_ERR_UNSUPPORTED;
 }
@@ -192,19 +150,10 @@ int qcn_conv12_fused_f32_nchw(const float* x, int nimg, float in_scale, int in_z
                               const float* u2, const float* v2, const float* mult2,
                               const int32_t* corr2, int y_zp, int relu2, const qcn_qdq_t* qdq2,
                               uint8_t* y, void* stream) {
-  using namespace qcn;
-  ConvEpi ep1{u1, v1, mult1, corr1, z1, relu1 ? z1 : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq1) { ep1.qdq = 1; ep1.s1 = qdq1->s1; ep1.z1 = qdq1->z1; ep1.inv2 = qdq1->inv2; ep1.z2 = qdq1->z2; }
-  ConvEpi ep2{u2, v2, mult2, corr2, y_zp, relu2 ? y_zp : 0, 0, 0.f, 0, 0.f, 0, 0};
-  if (qdq2) { ep2.qdq = 1; ep2.s1 = qdq2->s1; ep2.z1 = qdq2->z1; ep2.inv2 = qdq2->inv2; ep2.z2 = qdq2->z2; }
-  static bool attr_done[QCN_MAX_DEV] = {};
-  if (!qcn_set_lds_once((const void*)conv12p_stamped, Conv12P::LDS, attr_done)) return QCN_ERR_HIP;
-  const int ncu = qcn_cu_count();
-  if (ncu <= 0) return QCN_ERR_HIP;
-  const int grid = nimg < ncu ? nimg : ncu;
-  hipLaunchKernelGGL(conv12p_stamped, dim3(grid), dim3(512), Conv12P::LDS, (hipStream_t)stream, x,
-                     nimg, 1.0f / in_scale, in_zp, w1_packed, ep1, x2_zp, w2_packed, ep2, y);
-  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
+  if (!(in_scale > 0.f)) return QCN_ERR_ARG;
+  return qcn::conv12_fused<qcn::conv12p_stamped, qcn::Conv12P::LDS>(
+      x, nimg, 1.0f / in_scale, {w1_packed, u1, v1, mult1, corr1, in_zp, z1, relu1, qdq1},
+      {w2_packed, u2, v2, mult2, corr2, x2_zp, y_zp, relu2, qdq2}, y, stream);
 }
 
 // The one-launch conv1..conv6's stamps of the last launch: [wg][t0..t3, r0..r3]
