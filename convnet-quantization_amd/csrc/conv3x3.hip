@@ -1994,7 +1994,11 @@ void conv1_f32_kernel(const float* __restrict__ x, int nimg, float in_inv, int i
   store_staged<64, 80, 256>(lout, 512, y + p0 * 64, total - p0, tid);
 }
 
-using Conv2Cfg = ConvCfg<64, 64, 32, true, 4, 16, 96, 0, true>;
+// conv2 on the 16x16x64 MFMA: the Cin + 32 pixel stride (16 B x (2 mod 4))
+// makes every B-fragment ds_read_b128 conflict-free.  A 16-pixel block is 16
+// stride-2 columns of ONE patch row (parity-split: 16 consecutive slots), so
+// the row pad plays no part in the banking (tools/lds_banks.py) and is 0.
+using Conv2Cfg = ConvCfg<64, 64, 32, true, 4, 32, 0, 0, true>;
 
 // --------------------------------------------------------------------------
 // conv1 + conv2 fused, persistent and wave-specialised (the production path).
@@ -2010,13 +2014,23 @@ using Conv2Cfg = ConvCfg<64, 64, 32, true, 4, 16, 96, 0, true>;
 // hides behind the conv1 work.
 struct Conv12P {
   using C = Conv2Cfg;
-  static constexpr int PATCH = C::PATCH;
+  // The two half-image patches (18 rows each) share their one row that is
+  // never computed, conv2's zero-point padding row: row 0 of a top half, row
+  // 17 of a bottom half.  Even tiles are top halves and odd tiles bottom
+  // halves, so the buffers never swap kinds and lie as
+  //   [bottom half rows 0-16][the shared padding row][top half rows 1-17]
+  // with one row stride: 35 rows instead of 36.
+  static constexpr int ROWS = 2 * C::PROWS - 1;
+  static constexpr int OFF_BOT = 0;                        // odd tiles
+  static constexpr int OFF_TOP = (C::PROWS - 1) * C::RS;   // even tiles: row 0 is the shared row
+  static constexpr int PAD_ROW = C::PROWS - 1;             // the shared row, counted from OFF_BOT
+  static constexpr int PATCHES = ROWS * C::RS;
   static constexpr int WRES = 9 * C::WBUF;                 // all conv2 weights
   // quantized fp32 input window: rows y0-2..y0+17, cols -2..33, one dword per
   // pixel (c0, c1, c2, 0) so conv1's im2col operand is plain aligned dwords
   static constexpr int IN_R = 20, IN_C = 40;   // cols -4 .. 35: interior 16-B aligned
   static constexpr int IN8 = IN_R * IN_C * 4;
-  static constexpr int OFF_W = 2 * PATCH;
+  static constexpr int OFF_W = PATCHES;
   static constexpr int OFF_IN = OFF_W + WRES;              // 2 x quantized input window
   static constexpr int OFF_EPI1 = OFF_IN + 2 * IN8;
   static constexpr int OFF_EPI2 = OFF_EPI1 + 12 * 64;
@@ -2034,55 +2048,67 @@ struct Conv12P {
   static_assert(OFF_QLUT % 4 == 0 && LDS_U8 <= 160 * 1024, "LDS budget");
 };
 
-// conv_mainloop for weights resident in LDS (same swizzled chunk layout as the
-// ring, chunk ch at wres + ch * WBUF): a barrier-free, fully unrolled pipeline.
+// conv2's main loop on v_mfma_i32_16x16x64_i8 with all of its weights
+// resident in LDS (chunk s = tap s at wres + s * WBUF): a barrier-free, fully
+// unrolled pipeline with no weight traffic.  Wave wp owns all 64 couts x 128
+// pixels as 4 x 8 blocks of 16 x 16 (pipe_job16's tile); one K-step is one
+// tap: four A reads and eight B reads feed 32 MFMAs.  Lane (p, g) reads weight
+// row 16 i + p at K bytes 16 g .. 16 g + 15: row r's 16-B slot c is stored at
+// slot c ^ res16_swz(r), which spreads each ds_read_b128 lane group (rows
+// {0-3, 12-15} at slot g, {4-11} at slot g ^ 1) over all 64 banks
+// (tools/lds_banks.py).  A is double-buffered (step s + 1's fragment i read
+// after MFMA 4 i + 1 of step s), B single-buffered as in pipe_job16.
+QCN_DEV constexpr int res16_swz(int r) { return (4 - ((r >> 2) & 3)) & 3; }
+
 template <class C>
-QCN_DEV void conv_mainloop_res(const uint8_t* patch, const uint8_t* wres,
-                               const int* __restrict__ corr, int wave, int lane,
-                               v16i (&acc)[2][4]) {
-  constexpr int CB = C::kCin / 64;
-  const int wc = wave % C::WCO, wp = wave / C::WCO;
-  const int l32 = lane & 31, hi = lane >> 5;
-  const PatchAddr<C> pa(wp, l32, hi);
-  const int arow = wc * 64 + l32;
-  const int aswz = (arow >> 2) & 3;
-  v16i c0[2];   // the first K-step's C operand
+QCN_DEV void conv_mainloop_res16(const uint8_t* patch, const uint8_t* wres, const int* corr, int wp,
+                                 int p16, int g, v4i (&acc)[4][8]) {
+  using X = Pix16<C>;
+  constexpr int S = C::NCH;
+  static_assert(X::affine(), "pixel blocks at constant offsets");
+  static_assert(C::kCin == 64 && C::kCout == 64 && C::WCO == 1, "one tap per K-step, all couts per wave");
+  const int lb = X::at(wp, 0, p16) + 16 * g;
+  const int la = p16 * 64 + ((g ^ res16_swz(p16)) << 4);   // rows 16 i + p share p's swizzle
+  v4i c0[4];   // the first K-step's C operand: the zero-point correction
 #pragma unroll
-  for (int i = 0; i < 2; ++i) c0[i] = acc_init_corr(corr, wc * 64 + i * 32, hi);
-  const uint8_t* abase = wres + arow * 64;
-  auto rd_a = [&](int ch, int kk, int i) {
-    return *reinterpret_cast<const v4i*>(abase + ch * C::WBUF + i * 32 * 64 +
-                                         (((2 * kk + hi) ^ aswz) << 4));
+  for (int i = 0; i < 4; ++i) c0[i] = *reinterpret_cast<const v4i*>(corr + 16 * i + 4 * g);
+  auto rd_a = [&](int s, int i) {
+    return *reinterpret_cast<const v4i*>(wres + la + s * C::WBUF + i * 1024);
   };
-  auto rd_b = [&](int ch, int kk, int j) {
-    const int tap = ch / CB, cb = ch % CB;
-    return *reinterpret_cast<const v4i*>(patch + pa.base[j] + PatchAddr<C>::delta(tap, j) + cb * 64 +
-                                         kk * 32);
+  auto rd_b = [&](int s, int j) {
+    return *reinterpret_cast<const v4i*>(patch + lb + X::jofs(j) + PatchAddr<C>::delta(s, j));
   };
-  auto step = [&](v4i (&fan)[2], v4i (&fbn)[4], int rch, int rkk, bool rd,
-                  const v4i (&fa)[2], const v4i (&fb)[4], bool first) {
+  v4i fa[2][4], fb[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      if (rd) {
-        if (m < 2) fan[m] = rd_a(rch, rkk, m);
-        else if (m < 6) fbn[m - 2] = rd_b(rch, rkk, m - 2);
+  for (int i = 0; i < 4; ++i) fa[0][i] = rd_a(0, i);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) fb[j] = rd_b(0, j);
+  static_for<S>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    static_for<32>([&](auto mc) {
+      // pixel block outer, cout block inner; the first step the other way
+      // round, so that c0[i] dies after its eighth MFMA (the step that holds
+      // c0 beside all the accumulators is the register peak)
+      constexpr int m = decltype(mc)::value, j = s == 0 ? (m & 7) : (m >> 2), i = s == 0 ? (m >> 3) : (m & 3);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[s & 1][i], fb[j], s == 0 ? c0[i] : acc[i][j], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr ((m & 3) == 1 && m < 16 && s + 1 < S) {
+        // slot (s + 1) & 1 was step s - 1's: all its MFMAs have issued
+        fa[(s + 1) & 1][m >> 2] = rd_a(s + 1, m >> 2);
+        __builtin_amdgcn_sched_barrier(0);
       }
-      __builtin_amdgcn_sched_barrier(0);
-      acc[m >> 2][m & 3] = __builtin_amdgcn_mfma_i32_32x32x32_i8(
-          fa[m >> 2], fb[m & 3], first ? c0[m >> 2] : acc[m >> 2][m & 3], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  v4i fa0[2], fb0[4], fa1[2], fb1[4];
-  fa0[0] = rd_a(0, 0, 0);
-  fa0[1] = rd_a(0, 0, 1);
+      if constexpr (i == 3 && s + 1 < S) {
+        fb[j] = rd_b(s + 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    });
+    // pin the step's MFMAs here (as pipe_job16)
 #pragma unroll
-  for (int j = 0; j < 4; ++j) fb0[j] = rd_b(0, 0, j);
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-  for (int ch = 0; ch < C::NCH; ++ch) {
-    step(fa1, fb1, ch, 1, true, fa0, fb0, ch == 0);
-    step(fa0, fb0, ch + 1, 0, ch + 1 < C::NCH, fa1, fb1, false);
-  }
+      for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(acc[i][j]));
+  });
 }
 
 // Diagnostic builds only (tools/clock: -DQCN_C12_STAMP): s_memtime of lane 0
@@ -2126,32 +2152,54 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool producer = wave >= 4;
-  // window-staging thread id: producer waves 5-7 (0..191, 180 used).  Wave 4
-  // computes the most conv1 rows of a top half (5 of 17), so it stages none
-  const int ptid = tid - 320;
   // tile j of this workgroup: image t0 + (j / 2) * ts, top half then bottom
   // half (so every odd j reuses two conv1 rows from tile j - 1)
   auto tile_of = [&](int j) { return (t0 + (j >> 1) * ts) * 2 + (j & 1); };
-  uint8_t* patch0 = lds;
-  uint8_t* patch1 = lds + L::PATCH;
+  uint8_t* patch0 = lds + L::OFF_TOP;   // even tiles: top halves
+  uint8_t* patch1 = lds + L::OFF_BOT;   // odd tiles: bottom halves
   uint8_t* in8_0 = lds + L::OFF_IN;
   uint8_t* in8_1 = lds + L::OFF_IN + L::IN8;
 
   // the staged window row in flight: three float4 (fp32) or the 12 bytes of
-  // four RGB pixels as three dwords (u8)
-  typename std::conditional<U8, uint32_t, float4>::type xraw[3];
+  // four RGB pixels as three dwords (u8).  Declared where a producer loads
+  // and stores it (before the tile loop, and inside one iteration's producer
+  // branch), so it is never live across the consumer's MFMA region
+  using XRaw = typename std::conditional<U8, uint32_t, float4>::type;
+  // ... and defined there by an empty asm: a value undefined on the paths
+  // that load nothing was given a definition ahead of the tile loop, which
+  // made it live (and spilled) around the whole loop
+  auto def_xraw = [](XRaw (&xr)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (U8) asm volatile("" : "=v"(xr[c]));
+      else asm volatile("" : "=v"(xr[c].x), "=v"(xr[c].y), "=v"(xr[c].z), "=v"(xr[c].w));
+    }
+  };
+  // an epilogue's integer constants, made anew per tile: their float forms
+  // (the general requant's zero points and clamp) are then converted where
+  // they are used, not once ahead of the tile loop and held in VGPRs across it
+  auto fresh_epi = [](const ConvEpi& ep) {
+    ConvEpi e = ep;
+    asm volatile("" : "+s"(e.zp_y), "+s"(e.lo), "+s"(e.z1), "+s"(e.z2));
+    return e;
+  };
   const uint32_t padw = xor80(splat_u8(x2_zp));
   const uint4 pad4 = make_uint4(padw, padw, padw, padw);
-  for (int e = tid; e < 2 * C::PROWS * 8; e += 512) {
-    const int buf = e / (C::PROWS * 8), r = e % (C::PROWS * 8);
-    const int pr = r / 8, pc = ((r / 4) & 1) ? C::PCOLS - 1 : 0, chunk = r & 3;
-    *reinterpret_cast<uint4*>(lds + buf * L::PATCH + C::slot(0, pr, pc) + chunk * 16) = pad4;
+  // written once, never overwritten: the column halos of all 35 patch rows
+  // and the padding row the two patches share
+  int th = tid;
+  asm volatile("" : "+v"(th));   // a fresh copy: no tid-derived offset held across phases
+  for (int e = th; e < (2 * L::ROWS + C::PCOLS) * 4; e += 512) {
+    const int s = e >> 2, chunk = e & 3;
+    const int pr = s < 2 * L::ROWS ? s >> 1 : L::PAD_ROW;
+    const int pc = s < 2 * L::ROWS ? ((s & 1) ? C::PCOLS - 1 : 0) : s - 2 * L::ROWS;
+    *reinterpret_cast<uint4*>(lds + L::OFF_BOT + C::slot(0, pr, pc) + chunk * 16) = pad4;
   }
 
   // tables the tile loop reads (issued after the producer's first window
   // loads, so the two latencies overlap); run by the consumer waves
   auto setup = [&]() {
-    // ---- once per workgroup: resident conv2 weights (ring layout), epilogue
+    // ---- once per workgroup: resident conv2 weights (res16_swz rows), epilogue
     // constants of both layers, conv1's operand tables.  The weights go by
     // LDS-DMA (9 x 1 KB per consumer wave); the producer waves only load
     // their first input window meanwhile
@@ -2163,7 +2211,7 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
         const int o = p * 1024 + lane * 16;
         const int ch = o / C::WBUF, oc = o % C::WBUF;
         const int r = oc >> 6, sl = (oc >> 4) & 3;
-        glds16(w2 + (long)ch * C::WBUF + r * 64 + ((sl ^ ((r >> 2) & 3)) << 4), lds + L::OFF_W + p * 1024);
+        glds16(w2 + (long)ch * C::WBUF + r * 64 + ((sl ^ res16_swz(r)) << 4), lds + L::OFF_W + p * 1024);
       }
     }
 
@@ -2235,15 +2283,17 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
   // through an empty asm per use keeps LICM from hoisting loop-invariant
   // values out of the tile loop (they were spilled: the consumer's MFMA state
   // shares the register budget).
+  // Window-staging thread id: producer waves 5-7 (0..191, 180 used).  Wave 4
+  // computes the most conv1 rows of a top half (5 of 17), so it stages none.
   auto fresh_ptid = [&]() {
-    int v = ptid;
+    int v = tid;
     asm volatile("" : "+v"(v));
-    return v;
+    return v - 320;
   };
-  auto stage_load = [&](int t) {
-    if (ptid < 0) return;   // wave 4 (whole wave): no window share
-    const int n = t >> 1, y0 = (t & 1) * 16;
+  auto stage_load = [&](int t, XRaw (&xraw)[3]) {
     const int pt = fresh_ptid();
+    if (pt < 0) return;   // wave 4 (whole wave): no window share
+    const int n = t >> 1, y0 = (t & 1) * 16;
     const int r = pt < 144 ? pt >> 3 : 0, g = pt & 7;
     const int iy = y0 + (y0 == 0 ? 0 : -2) + r;   // rows 0..17 of the top half, 14..31 of the bottom
     const int nc = n < nimg ? n : nimg - 1;
@@ -2257,7 +2307,7 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
         xraw[c] = *reinterpret_cast<const float4*>(x + (((long)nc * 3 + c) * 32 + iy) * 32 + 4 * g);
     }
   };
-  auto stage_store = [&](uint8_t* in8, int half) {
+  auto stage_store = [&](uint8_t* in8, int half, const XRaw (&xraw)[3]) {
     const int pt = fresh_ptid();
     if (pt >= 0 && pt < 144) {
       const int rr = (half ? 0 : 2) + (pt >> 3), g = pt & 7;
@@ -2297,11 +2347,16 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
     asm volatile("" : "+v"(v));
     return v;
   };
+  // the wave id as a scalar, made anew per tile: what a tile derives from it
+  // (patch rows, output offsets) is that tile's SALU work, not VGPRs hoisted
+  // out of the tile loop (they were spilled around conv2's MFMA region)
+  auto wave_s = [&]() { return __builtin_amdgcn_readfirstlane(fresh(tid) >> 6); };
   bool vuni = false, muni = false;
   const bool fast1 = epi_fast(ep1);
   // conv2's patch for tile t: its 18 rows are conv1 rows y0 - 1 .. y0 + 16.
   // The row outside the image (row 0 of a top half, row 17 of a bottom half)
-  // is conv2's zero-point padding, written without computing it.  A bottom
+  // is conv2's zero-point padding: the row the two patches share, written
+  // once in the prologue.  A bottom
   // half right after its top half (prev != nullptr) copies rows 0 and 1
   // from rows 16 and 17 of the top half's patch (conv1 rows 15 and 16) instead
   // of recomputing them.  The remaining rows are computed as r0 + w,
@@ -2311,14 +2366,9 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
     // producer waves issue first: their VALU-bound conv1 is the longer phase,
     // the consumer's MFMAs fill the gaps (measured 53.6 vs 59.2 us)
     __builtin_amdgcn_s_setprio(kProdPrio);
-    const int h = t & 1, y0 = h * 16;
+    const int h = t & 1;
     const int r0 = h == 0 ? 1 : (prev ? 2 : 0), r1 = h == 0 ? 18 : 17;
-    const int ln = fresh(lane), l32 = ln & 31, hi = ln >> 5;
-    if (w == step - 1) {   // the wave with the fewest rows: the padding row
-      uint8_t* prow_ptr = pb + C::slot(0, h == 0 ? 0 : 17, l32 + 1);
-      *reinterpret_cast<uint4*>(prow_ptr + hi * 32) = pad4;
-      *reinterpret_cast<uint4*>(prow_ptr + hi * 32 + 16) = pad4;
-    }
+    const int ln = fresh(tid) & 63, l32 = ln & 31, hi = ln >> 5;
     if (prev) {   // rows 16, 17 of the top half -> rows 0, 1 (whole rows, halos included)
       for (int e = w * 64 + ln; e < 2 * C::RS / 16; e += step * 64)
         *reinterpret_cast<uint4*>(pb + C::slot(0, 0, 0) + e * 16) =
@@ -2382,20 +2432,15 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
           }
       }
       if constexpr (MODE == 0) {
+        const ConvEpi e1 = fresh_epi(ep1);
         for (int tr = r0 + w; tr < r1; tr += step) {
-          const int iy = y0 - 1 + tr;
           uint8_t* prow_ptr = pb + C::slot(0, tr, l32 + 1);
-          if (iy < 0 || iy >= 32) {  // wave-uniform: conv2's zero-point padding row
-            *reinterpret_cast<uint4*>(prow_ptr + hi * 32) = pad4;
-            *reinterpret_cast<uint4*>(prow_ptr + hi * 32 + 16) = pad4;
-            continue;
-          }
           v4i b0;
           bop(tr, b0);
 #pragma unroll
           for (int i = 0; i < 2; ++i) {
             v16i acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1[i], b0, c1[i], 0, 0, 0);
-            epilogue_tile_kf<1, true>(&acc, load_epik_lds(ek1, 64, i * 32, hi), ep1, i * 32, hi,
+            epilogue_tile_kf<1, true>(&acc, load_epik_lds(ek1, 64, i * 32, hi), e1, i * 32, hi,
                                       prow_ptr);
           }
         }
@@ -2403,7 +2448,7 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
         // rows w, w+4, ... of this producer wave, software-pipelined: the next
         // row's im2col reads and MFMAs are issued before this row's requant,
         // so the VALU never waits on an MFMA result (that cost ~40 s_nop per
-        // row).  Halo rows are computed like the others and then overwritten.
+        // row).
         const int wr = r0 + w;   // first row of this wave
         const int nr = (r1 - wr + step - 1) / step;
         auto mfma_row = [&](int tr, v16i (&acc)[2]) {
@@ -2446,11 +2491,6 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
               wd = __builtin_amdgcn_cvt_pk_u8_f32(t[i][2 * g + 1].y, 3, wd);
               pdw[i * 8 + 2 * g] = xor80(wd);   // channels i*32 + 8g + 4hi .. +3
             }
-          const int iy = y0 - 1 + tr;
-          if (iy < 0 || iy >= 32) {  // wave-uniform: conv2's zero-point padding row
-            *reinterpret_cast<uint4*>(prow_ptr + hi * 32) = pad4;
-            *reinterpret_cast<uint4*>(prow_ptr + hi * 32 + 16) = pad4;
-          }
         };
         // two named accumulator sets in ping-pong (a copy per row cost 16
         // v_mov_b64): row kr+1's im2col reads and MFMAs go out before row kr's
@@ -2480,26 +2520,59 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
     }
   };
   auto conv2_tile = [&](int t, const uint8_t* pb) {
-    const int ln = fresh(lane), l32 = ln & 31, hi = ln >> 5;
-    v16i acc[2][4];
-    conv_mainloop_res<C>(pb, lds + L::OFF_W, reinterpret_cast<const int*>(lds + L::OFF_CORR2),
-                         wave, ln, acc);
+    const int ln = fresh(tid) & 63, p16 = ln & 15, g = ln >> 4;
+    const int wv = wave_s();
+    v4i acc[4][8];
+    conv_mainloop_res16<C>(pb, lds + L::OFF_W, reinterpret_cast<const int*>(lds + L::OFF_CORR2), wv, p16, g,
+                           acc);
     C12_STAMP(((t >> 1) - t0) / ts * 2 + (t & 1) + 1, 2);
     const int n = t >> 1, h = t & 1;
     const float* ek2 = reinterpret_cast<const float*>(lds + L::OFF_EPI2);
-    uint8_t* dst = y + ((long)n * 256 + h * 128 + wave * 32 + l32) * 64;
-    const uint8_t* wbase = y + ((long)n * 256 + h * 128) * 64;   // write-through destination
-    const uint32_t woff = (uint32_t)((wave * 32 + l32) * 64);
+    const ConvEpi e2 = fresh_epi(ep2);
+    // write-through destination: this wave's 32 pooled pixels x 64 channels of the half image
+    const wt_rsrc_t wr = wt_rsrc(y + ((long)n * 256 + h * 128 + wv * 32) * 64);
+    // The pooled epilogue of convpair_ws16_body::epi_b: per group of 16 pooled
+    // pixels (one pooled row) the max over the four quadrant blocks, requant,
+    // a 4 x 4 dword transpose across the lane groups and one 16-B store per lane
+    auto epi = [&](auto mode) {
+      constexpr int EM = decltype(mode)::value;
+      static_for<2>([&](auto gc) {
+        constexpr int gq = decltype(gc)::value;
+        uint32_t d[4];
+        static_for<4>([&](auto ic) {
+          constexpr int i = decltype(ic)::value;
+          const EpiG K = load_epig(ek2, 64, 16 * i + 4 * g);
+          uint32_t wd = 0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-      epilogue_tile_kf<4, false, false, true>(acc[i], load_epik_lds(ek2, 64, i * 32, hi), ep2, i * 32, hi,
-                                              dst, wbase, woff);
+          for (int r = 0; r < 4; ++r) {
+            const int a = max(max(acc[i][4 * gq][r], acc[i][4 * gq + 1][r]),
+                              max(acc[i][4 * gq + 2][r], acc[i][4 * gq + 3][r]));
+            wd = rq_elem<EM>(a, K, r, e2, wd);
+          }
+          d[i] = wd;
+        });
+        const auto s02 = __builtin_amdgcn_permlane32_swap(d[0], d[2], false, false);
+        const auto s13 = __builtin_amdgcn_permlane32_swap(d[1], d[3], false, false);
+        const auto t01 = __builtin_amdgcn_permlane16_swap(s02[0], s13[0], false, false);
+        const auto t23 = __builtin_amdgcn_permlane16_swap(s02[1], s13[1], false, false);
+        // channels 16 g .. 16 g + 15 of the wave's pooled pixel 16 gq + p16
+        store_wt16(wr, (uint32_t)((16 * gq + p16) * 64 + 16 * g),
+                   make_uint4(t01[0], t01[1], t23[0], t23[1]));
+      });
+    };
+    if (epi_fast(e2)) epi(std::integral_constant<int, 1>{});
+    else if (e2.qdq == 2) epi(std::integral_constant<int, 2>{});
+    else epi(std::integral_constant<int, 0>{});
   };
 
-  if (producer && T > 0) stage_load(tile_of(0));
-  setup();
-  if constexpr (U8) __syncthreads();   // the table is written by other threads than read it
-  if (producer && T > 0) stage_store(in8_0, 0);
+  {
+    XRaw xraw[3];
+    def_xraw(xraw);
+    if (producer && T > 0) stage_load(tile_of(0), xraw);
+    setup();
+    if constexpr (U8) __syncthreads();   // the table is written by other threads than read it
+    if (producer && T > 0) stage_store(in8_0, 0, xraw);
+  }
   if (!producer) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // own weight DMA landed
   __syncthreads();
   // conv1 requant specialisation: v (and mult) identical across channels —
@@ -2514,18 +2587,21 @@ QCN_DEV void conv12p_body(int t0, int ts, int T, const XT* __restrict__ x, int n
   for (int j = 0; j <= T; ++j) {
     C12_STAMP(j, 0);
     if (producer) {
-      if (j + 1 < T) stage_load(tile_of(j + 1));
+      XRaw xraw[3];
+      def_xraw(xraw);
+      if (j + 1 < T) stage_load(tile_of(j + 1), xraw);
       if (j < T) {
         // the first tile's conv1 is split with the (otherwise idle) consumer waves
         const bool split = SPLIT0 && j == 0;
+        const int wv = wave_s();
         conv1_tile(tile_of(j), (j & 1) ? in8_1 : in8_0, (j & 1) ? patch1 : patch0,
-                   (j & 1) ? patch0 : nullptr, split ? wave : wave - 4, split ? 8 : 4);
+                   (j & 1) ? patch0 : nullptr, split ? wv : wv - 4, split ? 8 : 4);
       }
-      if (j + 1 < T) stage_store(((j + 1) & 1) ? in8_1 : in8_0, (j + 1) & 1);
+      if (j + 1 < T) stage_store(((j + 1) & 1) ? in8_1 : in8_0, (j + 1) & 1, xraw);
     } else if (j >= 1) {
       conv2_tile(tile_of(j - 1), ((j - 1) & 1) ? patch1 : patch0);
     } else if (SPLIT0 && T > 0) {
-      conv1_tile(tile_of(0), in8_0, patch0, nullptr, wave, 8);
+      conv1_tile(tile_of(0), in8_0, patch0, nullptr, wave_s(), 8);
       __builtin_amdgcn_s_setprio(0);
     }
     C12_STAMP(j, 1);

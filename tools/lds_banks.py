@@ -110,7 +110,8 @@ def check(cfg, shape):
 
 # the headline's patch layouts (ConvCfg arguments in conv3x3.hip)
 HEADLINE = [
-    ("conv2 (Conv2Cfg)", dict(cin=64, hw=32, pool=True, wpx=4, psp=16, rpad=96, spad=0, split=True, segs=1)),
+    ("conv2 (Conv2Cfg)", dict(cin=64, hw=32, pool=True, wpx=4, psp=32, rpad=0, spad=0, split=True, segs=1)),
+    ("conv2 (r04 patch)", dict(cin=64, hw=32, pool=True, wpx=4, psp=16, rpad=96, spad=0, split=True, segs=1)),
     ("conv3 (WsA3)", dict(cin=64, hw=16, pool=False, wpx=2, psp=16, rpad=96, spad=0, split=False)),
     ("conv4 (WsB4)", dict(cin=128, hw=16, pool=True, wpx=2, psp=16, rpad=32, spad=0, split=True)),
     ("conv5 (WsA5)", dict(cin=128, hw=8, pool=False, wpx=1, psp=16, rpad=224, spad=0, split=False, segs=2)),
@@ -131,6 +132,74 @@ def make(name, kw):
     return conv2_tile(kw) if name.startswith("conv2") else Cfg(**kw, name=name)
 
 
+# conv2's resident weights (conv12, conv_mainloop_res16): chunk s at s * 4096,
+# row r (cout) 64 B, its 16-B slot c stored at slot c ^ swz(r)
+def res16_swz(r):
+    return (4 - ((r >> 2) & 3)) & 3
+
+
+def ring_swz(r):
+    return (r >> 2) & 3
+
+
+def check_a16(swz=res16_swz):
+    """(worst, mean) cycles over the A-fragment reads of conv2's 16x16x64 loop:
+    lane (p, g) reads row 16 i + p, K bytes 16 g .. 16 g + 15, of every chunk."""
+    worst, tot, n = 0, 0, 0
+    for s in range(9):
+        for i in range(4):
+            addrs = []
+            for l in range(64):
+                p, g = l & 15, l >> 4
+                r = 16 * i + p
+                addrs.append(s * 4096 + r * 64 + ((g ^ swz(r)) << 4))
+            c = read_cycles(addrs)
+            worst, tot, n = max(worst, c), tot + c, n + 1
+    return worst, tot / n
+
+
+def conflicted(name, kw, shape="16"):
+    """Number of conflicted B-fragment reads (more than 4 cycles) of a layout."""
+    c = make(name, kw)
+    nj = 4 if shape == "32" else 8
+    bad = 0
+    for wp in range(c.wpx):
+        for j in range(nj):
+            for tap in range(9):
+                addrs = []
+                for l in range(64):
+                    p, k = (l & 15, (l >> 4) * 16) if shape == "16" else (l & 31, (l >> 5) * 16)
+                    seg, pr, pc, par = c.pixel(shape, wp, j, p)
+                    addrs.append(c.slot(seg, pr, pc) + c.delta(tap, par) + k)
+                bad += read_cycles(addrs) > 4
+    return bad
+
+
+def conv1_write_ways(cfg):
+    """Worst N-way conflict of the conv12 producer's ds_write_b32 into conv2's
+    patch: 2 groups of 32 lanes, bank (a / 4) mod 32; lane (l32, hi) writes
+    dword hi of a channel group of pixel column l32 + 1 of one patch row."""
+    worst = 0
+    for hi in range(2):
+        banks = {}
+        for l32 in range(32):
+            a = cfg.slot(0, 1, l32 + 1) + 4 * hi
+            banks.setdefault((a // 4) % 32, set()).add(a // 4)
+        worst = max(worst, max(len(v) for v in banks.values()))
+    return worst
+
+
+def conv12_lds(cfg):
+    """Conv12P's LDS plan (bytes): the two half-image patches around their one
+    shared padding row, the resident weights, two input windows, the tables."""
+    rows = 2 * cfg.PROWS - 1
+    patches = rows * cfg.RS
+    wres, win, tab = 9 * 64 * 64, 2 * 20 * 40 * 4, 2 * 768 + 256 + 2048 + 256
+    total = patches + wres + win + tab
+    return dict(rows=rows, row_stride=cfg.RS, patches=patches, weights=wres, windows=win, tables=tab,
+                total=total, total_u8=total + 768, limit=160 * 1024)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--search", action="store_true")
@@ -141,6 +210,18 @@ def main():
             w, m = check(c, shape)
             print(f"{name:18s} {shape}x{shape}: worst {w} cyc (4 = conflict-free), mean {m:.2f}, "
                   f"patch {c.patch} B")
+    # conv12's conv2 on the 16x16x64 MFMA: B and A fragments, conv1's writes, the LDS plan
+    name, kw = HEADLINE[0]
+    c2 = make(name, kw)
+    print(f"conv2 16x16 B fragments: {conflicted(name, kw)} conflicted reads of {c2.wpx * 8 * 9}")
+    for label, swz in (("res16_swz", res16_swz), ("ring swizzle", ring_swz)):
+        w, m = check_a16(swz)
+        print(f"conv2 16x16 A fragments ({label}): worst {w} cyc, mean {m:.2f}")
+    for nm, k2 in HEADLINE[:2]:
+        print(f"{nm}: conv1's ds_write_b32 into the patch {conv1_write_ways(make(nm, k2))}-way "
+              "(2-way is free, 4-way 2x, 8-way 4x the LDS cycles)")
+    plan = conv12_lds(c2)
+    print("conv12 LDS plan:", ", ".join(f"{k} {v}" for k, v in plan.items()))
     if not args.search:
         return
     for name, kw in HEADLINE:
