@@ -111,7 +111,12 @@ class CustomQuantizedResNet50(nn.Module):
     as ``qconvnet.resnet_qdq.QuantizedResNetQDQ``."""
 
     def __init__(self, model, conv1_scale=1.0, calibration_batches=None, device="cuda",
-                 per_channel=True, mode="static", mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD):
+                 per_channel=True, mode="static", mean=data.IMAGENET_MEAN, std=data.IMAGENET_STD,
+                 observer="minmax", calibration_device="cpu"):
+        """observer: "minmax" (default) or "histogram" (torch.ao's default
+        HistogramObserver, reduce_range=False); calibration_device: where the
+        fp32 calibration forward runs ("cpu": reproducible; "cuda": the HIP
+        observer kernels)."""
         from qconvnet.resnet import quantize_resnet
         from qconvnet.resnet_qdq import quantize_resnet_reference
         from models.resnet import synthetic_images
@@ -124,7 +129,23 @@ class CustomQuantizedResNet50(nn.Module):
         self.conv1_scale = conv1_scale
         self.mode = mode
         build = quantize_resnet if mode == "static" else quantize_resnet_reference
-        self.quantized_model = build(model.eval(), batches, device, per_channel, mean=mean, std=std)
+        # kept (not a submodule: state_dict() stays as it was) for quantization_report
+        object.__setattr__(self, "fp32_model", model.eval())
+        self.quantized_model = build(self.fp32_model, batches, device, per_channel,
+                                     calibration_device=calibration_device, mean=mean, std=std,
+                                     observer=observer)
+
+    def quantization_report(self, images, batch=32):
+        """Per-layer quantization error of ``images`` (fp32 NCHW or raw uint8
+        NHWC) at every hand-off of the int8 net against the fp32 model it was
+        built from: qconvnet.resnet.layer_report (mode="static") or
+        qconvnet.resnet_qdq.layer_report (mode="reference")."""
+        sd = self.fp32_model.state_dict()
+        if self.mode == "static":
+            from qconvnet.resnet import fold_state_dict, layer_report
+            return layer_report(self.quantized_model, fold_state_dict(sd), images, batch)
+        from qconvnet.resnet_qdq import layer_report, unfolded_state
+        return layer_report(self.quantized_model, unfolded_state(sd), images, batch)
 
     def forward(self, x):
         return self.quantized_model(x)

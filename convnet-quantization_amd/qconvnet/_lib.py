@@ -67,6 +67,8 @@ SIGNATURES = {
     "qcn_eval_topk_f32": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp]),
     "qcn_qerror_workspace_size": (i64, [i32, i32, i32, i32]),
     "qcn_qerror_u8_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp]),
+    "qcn_qerror_f32_workspace_size": (i64, [i32, i32, i32, i32]),
+    "qcn_qerror_f32_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "qcn_resize_crop_workspace_size": (i64, [C.POINTER(ResizeImg), i32, i32, i32]),
     "qcn_resize_crop_tap_stride": (i32, [C.POINTER(ResizeImg), i32, i32, i32]),
     "qcn_resize_crop_u8_hwc": (i32, [vp, i64, C.POINTER(ResizeImg), vp, i32, i32, i32, vp, vp, vp]),

@@ -261,6 +261,58 @@ def qerror(x, q, scale, zero_point, counts, sums, nhwc=True, workspace=None):
     return workspace
 
 
+def qerror_f32_workspace_size(n, c, h, w):
+    """Bytes of qerror_f32's workspace for an [n,c,h,w] activation (host arithmetic)."""
+    size = lib().qcn_qerror_f32_workspace_size(int(n), int(c), int(h), int(w))
+    if size < 0:
+        raise ValueError(f"qerror_f32_workspace_size: bad shape {(n, c, h, w)} ({size})")
+    return size
+
+
+def qerror_f32_buffers(channels, device):
+    """Zeroed (counts int64 [channels, 3], sums float64 [channels, 4]) for qerror_f32."""
+    return (torch.zeros((int(channels), 3), dtype=torch.int64, device=device),
+            torch.zeros((int(channels), 4), dtype=torch.float64, device=device))
+
+
+def qerror_f32(x, y, counts, sums, nhwc=True, workspace=None):
+    """ADDS the per-channel error statistics of the fp32 activation ``y``
+    (NHWC [n,h,w,c] when ``nhwc`` else NCHW; [rows, c] either way) against its
+    fp32 reference ``x`` (NCHW [n,c,h,w] or [rows, c]) into ``counts`` /
+    ``sums`` (qerror_f32_buffers; the fields are qcn_qerror_f32_f32's,
+    include/qconvnet.h).  Both may start at any 4-byte boundary.
+    ``workspace``: a device uint8 tensor of at least qerror_f32_workspace_size
+    bytes (one is made when None; concurrent streams need their own, and their
+    own ``sums``).  No sync.  Returns the workspace."""
+    _need(x, torch.float32, "qerror_f32.x")
+    _need(y, torch.float32, "qerror_f32.y")
+    if x.dim() == 2:
+        n, c = x.shape
+        h = w = 1
+    elif x.dim() == 4:
+        n, c, h, w = x.shape
+    else:
+        raise ValueError("qerror_f32.x: expected [n,c,h,w] or [rows,c]")
+    want = (n, c) if x.dim() == 2 else ((n, h, w, c) if nhwc else (n, c, h, w))
+    if tuple(y.shape) != want:
+        raise ValueError(f"qerror_f32.y: expected shape {want}, got {tuple(y.shape)}")
+    _need(counts, torch.int64, "qerror_f32.counts")
+    _need(sums, torch.float64, "qerror_f32.sums")
+    if counts.numel() != 3 * c or sums.numel() != 4 * c:
+        raise ValueError("qerror_f32: expected counts [c, 3] and sums [c, 4]")
+    need = qerror_f32_workspace_size(n, c, h, w)
+    if workspace is None:
+        workspace = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    _need(workspace, torch.uint8, "qerror_f32.workspace")
+    if workspace.numel() < need:
+        raise ValueError(f"qerror_f32.workspace: {need} bytes needed")
+    if n == 0:   # nothing to add (an empty tensor has no address to pass)
+        return workspace
+    check(lib().qcn_qerror_f32_f32(_ptr(x), _ptr(y), n, c, h, w, int(bool(nhwc)), _ptr(counts),
+                                   _ptr(sums), _ptr(workspace), _stream()), "qerror_f32")
+    return workspace
+
+
 def _resize_desc(desc):
     from .preprocess import DESC
     if not isinstance(desc, np.ndarray) or desc.dtype != DESC or desc.ndim != 1:

@@ -15,8 +15,15 @@ the channels combined (sums summed, the max of the max):
   sqnr_db = 10 log10(sum_x2 / sum_e2) (torch.ao.ns.fx.utils.compute_sqnr),
   mse, mean_abs_err, below_frac, above_frac, differ_frac.
 
-Not covered: the ResNet executors, the dynamic models, and a reduction over
-ranks (max_abs_err is not a sum).
+``FloatErrorStats`` is the twin for an fp32 activation against its fp32
+reference (qcn_qerror_f32_f32): count, differ (x != y),
+max_abs_err, sum_x2, sum_e2, sum_abs_e, sum_e (signed); sqnr_db, mse,
+mean_abs_err, mean_err, differ_frac.  The ResNet executors' reports
+(qconvnet.resnet / qconvnet.resnet_qdq: layer_names, layer_pairs,
+layer_report) are built on the two.
+
+Not covered: the dynamic models, and a reduction over ranks (max_abs_err is
+not a sum).
 """
 from __future__ import annotations
 
@@ -118,15 +125,118 @@ class QuantErrorStats:
         return self
 
 
-def _conv_deterministic(x, w, b):
+RAW_F32 = ("count", "differ", "max_abs_err", "sum_x2", "sum_e2", "sum_abs_e", "sum_e")
+DERIVED_F32 = ("sqnr_db", "mse", "mean_abs_err", "mean_err", "differ_frac")
+
+
+def _derive_f32(r):
+    n = np.maximum(r["count"], 1).astype(np.float64)
+    r["sqnr_db"] = _sqnr_db(r["sum_x2"], r["sum_e2"])
+    r["mse"] = r["sum_e2"] / n
+    r["mean_abs_err"] = r["sum_abs_e"] / n
+    r["mean_err"] = r["sum_e"] / n
+    r["differ_frac"] = r["differ"] / n
+    return r
+
+
+def summarize_f32(counts, sums):
+    """Host only: the report of int64 ``counts`` [c, 3] and float64 ``sums``
+    [c, 4] as qcn_qerror_f32_f32 leaves them — a dict of numpy arrays [c]
+    (RAW_F32 and DERIVED_F32 fields; differ counts x != y, mean_err is the
+    signed mean of x - y) plus "tensor", the same fields as scalars for the
+    channels combined.  sqnr_db follows summarize()'s +-inf / nan rules."""
+    counts = np.ascontiguousarray(counts, np.int64).reshape(-1, 3)
+    sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 4)
+    if counts.shape[0] != sums.shape[0]:
+        raise ValueError("summarize_f32: counts [c, 3] and sums [c, 4] of the same c")
+    r = {"count": counts[:, 0].copy(), "differ": counts[:, 1].copy(),
+         "max_abs_err": counts[:, 2].astype(np.uint32).view(np.float32).copy(),
+         "sum_x2": sums[:, 0].copy(), "sum_e2": sums[:, 1].copy(), "sum_abs_e": sums[:, 2].copy(),
+         "sum_e": sums[:, 3].copy()}
+    t = {k: r[k].sum() for k in RAW_F32 if k != "max_abs_err"}
+    t["max_abs_err"] = r["max_abs_err"].max() if len(r["max_abs_err"]) else np.float32(0)
+    r = _derive_f32(r)
+    r["tensor"] = {k: v[()] for k, v in _derive_f32({k: np.asarray(v) for k, v in t.items()}).items()}
+    return r
+
+
+class FloatErrorStats:
+    """QuantErrorStats' twin for an fp32 activation against its fp32
+    reference (qcn_qerror_f32_f32, ops.qerror_f32): one buffer, no sync until
+    ``result()``, one copy there."""
+
+    def __init__(self, channels, device="cuda"):
+        from .qmodel import cuda_device
+        self.channels = int(channels)
+        if self.channels < 1:
+            raise ValueError("FloatErrorStats: expected at least one channel")
+        self.device = cuda_device(device)
+        c = self.channels
+        self._buf = torch.zeros(7 * c, dtype=torch.int64, device=self.device)
+        self.counts = self._buf[:3 * c].view(c, 3)
+        self.sums = self._buf[3 * c:].view(torch.float64).view(c, 4)
+        self._ws = None
+
+    def update(self, x, y, nhwc=True):
+        """Add one batch: ``x`` device fp32 [n, channels, h, w] or [rows,
+        channels]; ``y`` the fp32 activation (NHWC when ``nhwc``).  Launches on
+        the current stream of the device; no sync."""
+        if not (x.is_cuda and y.is_cuda):
+            raise ValueError("FloatErrorStats.update: expected device tensors")
+        if x.dim() not in (2, 4) or x.shape[1] != self.channels:
+            raise ValueError(f"FloatErrorStats.update: expected {self.channels} channels")
+        with torch.cuda.device(self.device):
+            h, w = (x.shape[2], x.shape[3]) if x.dim() == 4 else (1, 1)
+            need = ops.qerror_f32_workspace_size(x.shape[0], self.channels, h, w)
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(max(need, 8), dtype=torch.uint8, device=self.device)
+            ops.qerror_f32(x.contiguous(), y.contiguous(), self.counts, self.sums, nhwc=nhwc,
+                           workspace=self._ws)
+        return self
+
+    def result(self):
+        """ONE device-to-host copy (it waits for the current stream);
+        summarize_f32() of the counts and sums."""
+        with torch.cuda.device(self.device):
+            raw = self._buf.cpu().numpy()
+        c = self.channels
+        return summarize_f32(raw[:3 * c], raw[3 * c:].view(np.float64))
+
+    def reset(self):
+        self._buf.zero_()
+        return self
+
+
+def _conv_deterministic(x, w, b, stride=1, padding=1):
     """F.conv2d with a deterministic algorithm (the default choice for the
     8x8 layers at small batches adds in a varying order)."""
     prev = torch.backends.cudnn.deterministic
     torch.backends.cudnn.deterministic = True
     try:
-        return F.conv2d(x, w, b, padding=1)
+        return F.conv2d(x, w, b, stride=stride, padding=padding)
     finally:
         torch.backends.cudnn.deterministic = prev
+
+
+def score_pairs(pairs, device):
+    """{name: result} in first-seen order for an iterable of (name, x_fp32,
+    y, scale, zero_point, nhwc): a u8 ``y`` is scored by a QuantErrorStats
+    with (scale, zero_point), an fp32 ``y`` by a FloatErrorStats; one stats
+    object per name, one synchronisation, at the end."""
+    stats = {}
+    for name, x, y, scale, zp, nhwc in pairs:
+        st = stats.get(name)
+        if y.dtype == torch.uint8:
+            if st is None:
+                st = stats[name] = QuantErrorStats(x.shape[1], device)
+            st.update(x, y, scale, zp, nhwc)
+        else:
+            if st is None:
+                st = stats[name] = FloatErrorStats(x.shape[1], device)
+            st.update(x, y, nhwc)
+    if not stats:
+        raise ValueError("layer_report: no images")
+    return {name: st.result() for name, st in stats.items()}
 
 
 def layer_names(mode):

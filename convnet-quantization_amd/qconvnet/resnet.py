@@ -29,7 +29,7 @@ import torch.nn.functional as F
 from . import ops
 from . import quant as Q
 from .data import IMAGENET_MEAN, IMAGENET_STD
-from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device, normalized_input
+from .qmodel import _OBSERVERS, _DevLayer, _weight_scale, cuda_device, normalized_input
 
 F32 = np.float32
 
@@ -69,7 +69,8 @@ def fold_state_dict(sd):
 
 
 # ============================================================ calibration
-def calibrate(folded, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+def calibrate(folded, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+              observer="minmax"):
     """fp32 forward of the folded net recording every observer's range
     (batches: normalised fp32 NCHW, or raw uint8 NHWC images normalised here
     with ``mean`` / ``std``):
@@ -77,7 +78,18 @@ def calibrate(folded, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_ST
     out (post add+ReLU), fc.  On the CPU (the default) the ranges are those
     torch.ao's observers record on the same host (same fp32 ops, same folded
     weights) and do not change from run to run; device="cuda" uses the HIP
-    min/max observer behind MIOpen's fp32 convs (faster, not bit-stable)."""
+    min/max observer behind MIOpen's fp32 convs (faster, not bit-stable).
+
+    observer="histogram": torch.ao's default HistogramObserver (2048 bins,
+    reduce_range=False) at the same points; the range is its searched
+    clipping range, so Q.qparams_affine of it is calculate_qparams().  The
+    points are where torch.ao's output observers of the fused ConvReLU2d /
+    Conv2d modules and the stubs sit (stem, c1, c2 after their ReLU; c3, ds,
+    fc raw; out after add + ReLU), so no observation point moves.  On
+    device="cuda" the histogram is ops.HistogramObserver (qcn_histc_f32)."""
+    if observer not in _OBSERVERS:
+        raise ValueError(f"unknown observer {observer!r} (expected one of {sorted(_OBSERVERS)})")
+    make = _OBSERVERS[observer]
     dev = torch.device(device)
 
     def t(a):
@@ -86,11 +98,11 @@ def calibrate(folded, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_ST
     stem = [t(a) for a in folded["stem"]]
     blocks = [{k: (t(v[0]), t(v[1]), v[2], v[3]) for k, v in b.items()} for b in folded["blocks"]]
     fc = [t(a) for a in folded["fc"]]
-    rng = {"x": _Range(dev), "stem": _Range(dev), "fc": _Range(dev)}
+    rng = {"x": make(dev), "stem": make(dev), "fc": make(dev)}
     ntab = Q.normalize_table(mean, std).to(dev)
     for i, b in enumerate(blocks):
         for k in list(b) + ["out"]:
-            rng[f"b{i}.{k}"] = _Range(dev)
+            rng[f"b{i}.{k}"] = make(dev)
     with torch.no_grad():
         for xb in batches:
             x = normalized_input(xb, dev, ntab)
@@ -157,12 +169,13 @@ def build_spec(folded, ranges, per_channel=True):
 
 
 def quantize_resnet(model, calib_batches, device="cuda", per_channel=True, calibration_device="cpu",
-                    mean=IMAGENET_MEAN, std=IMAGENET_STD):
+                    mean=IMAGENET_MEAN, std=IMAGENET_STD, observer="minmax"):
     """fp32 ResNet (models.resnet / torchvision layout) -> QuantizedResNet on
     `device`; calibration runs on `calibration_device` (CPU: deterministic).
-    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference)."""
+    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference);
+    ``observer``: "minmax" or "histogram" (calibrate)."""
     folded = fold_state_dict(model.state_dict())
-    ranges = calibrate(folded, calib_batches, calibration_device, mean, std)
+    ranges = calibrate(folded, calib_batches, calibration_device, mean, std, observer)
     return QuantizedResNet(build_spec(folded, ranges, per_channel), device, mean, std)
 
 
@@ -282,7 +295,11 @@ class QuantizedResNet:
 
     def run(self, x, keep=False, marks=None):
         """The whole int8 forward on the current stream of the model's device
-        (no sync)."""
+        (no sync).  keep=True also returns the block outputs; keep="layers" is
+        the inspection mode of the error report: the three-launch stem, every
+        conv its own launch, conv3 without the join and then ops.add_relu —
+        the same bits, with "stem.conv" (pre-pool), "block{i}.c1" / ".c2" /
+        ".c3" (pre-add) / ".ds" and the u8 logits "fc.q" kept as well."""
         if x.device != self.device:
             raise ValueError(f"input on {x.device}, model on {self.device}")
         with torch.cuda.device(self.device):
@@ -346,7 +363,10 @@ class QuantizedResNet:
         sp = self.spec
         mark("start")
         u8 = x.dtype == torch.uint8   # raw images: the QuantStub is a lookup in qlut
-        if self._stem_fusable(x):   # quantize + conv + ReLU + max-pool in one launch
+        layers = isinstance(keep, str) and keep == "layers"
+        if keep not in (False, True) and not layers:
+            raise ValueError(f"unknown keep {keep!r}")
+        if self._stem_fusable(x) and not layers:   # quantize + conv + ReLU + max-pool in one launch
             if u8:
                 q = ops.stem_fused_u8(x, self.qlut, self.in_zp, self.stem)
             else:
@@ -363,6 +383,8 @@ class QuantizedResNet:
             q = ops.conv(q, self.in_zp, self.stem)
             mark("conv")
             yield
+            if layers:
+                inter["stem.conv"] = q
             q = ops.maxpool3x3s2(q)
             mark("maxpool")
             yield
@@ -384,6 +406,7 @@ class QuantizedResNet:
                 y = ops.conv(q, zx, b["c1"])
                 mark("conv")
                 yield
+            y1 = y
             yh = self._conv3x3_halo(y, b["c2"])
             y = yh if yh is not None else ops.conv(y, b["c2"].z_x, b["c2"])
             mark("conv")
@@ -393,14 +416,23 @@ class QuantizedResNet:
             # conv where the shapes allow (its input is this join's output)
             nb = self.blocks[i + 1] if i + 1 < len(self.blocks) else None
             fused = None
-            if self.fuse_reduce and nb is not None and self._join_reduce_fusable(b["c3"], nb["c1"]):
+            if (not layers and self.fuse_reduce and nb is not None
+                    and self._join_reduce_fusable(b["c3"], nb["c1"])):
                 assert nb["c1"].z_x == int(zo), "the next reduce reads this join's output"
                 fused = ops.conv_join_reduce(y, b["c3"].z_x, b["c3"], (idn, si, zi, so, zo), nb["c1"])
             if fused is not None:
                 q, pending = fused
+            elif layers:
+                y3 = ops.conv(y, b["c3"].z_x, b["c3"])
+                mark("conv")
+                yield
+                q = ops.add_relu(y3, e["c3"]["s_y"], e["c3"]["z_y"], idn, si, zi, so, zo)
+                inter.update({f"block{i}.c1": y1, f"block{i}.c2": y, f"block{i}.c3": y3})
+                if b["ds"] is not None:
+                    inter[f"block{i}.ds"] = idn
             else:
                 q = ops.conv(y, b["c3"].z_x, b["c3"], resid=(idn, si, zi, so, zo))
-            mark("conv")
+            mark("add_relu" if layers else "conv")
             yield
             if keep:
                 inter[f"block{i}"] = q
@@ -414,6 +446,8 @@ class QuantizedResNet:
         qy, logits = ops.linear_u8(q, f.z_x, f.w, f.u, f.v, f.mult, f.corr, f.z_y, False,
                                    y_scale=f.s_y, want_fp32=True)
         mark("fc")
+        if layers:
+            inter["fc.q"] = qy
         return (logits, inter) if keep else logits
 
     def capture_graph(self, x_static):
@@ -468,3 +502,83 @@ class QuantizedResNet:
     def cuda(self, device=None):
         self.host_io = False
         return self
+
+
+# ============================================================ error report
+def layer_names(qmodel):
+    """The hand-offs layer_pairs scores, in forward order, under the
+    observers' names (calibrate)."""
+    names = ["x", "stem"]
+    for i, b in enumerate(qmodel.blocks):
+        names += [f"b{i}.c1", f"b{i}.c2", f"b{i}.c3"]
+        names += ([f"b{i}.ds"] if b["ds"] is not None else []) + [f"b{i}.out"]
+    return names + ["pool", "fc"]
+
+
+def layer_pairs(qmodel, folded, images, batch=32):
+    """Yield (name, x_fp32, q_u8, scale, zero_point, nhwc) for every hand-off
+    of ``qmodel`` (a QuantizedResNet), batch by batch, in layer_names order
+    within a batch.  ``folded``: fold_state_dict of the fp32 model it was built
+    from; ``images``: fp32 NCHW, or raw uint8 NHWC (normalised with the model's
+    mean / std), host or device.
+
+    Per batch, on the model's device and current stream: ``qmodel.run(x,
+    keep="layers")`` and the walk of calibrate() through torch ops (fp32 convs
+    with a deterministic algorithm), one layer's reference at a time:
+      "x":        the input against ops.quantize of it;
+      "stem":     post-ReLU against the pre-pool stem conv;
+      b{i}.c1/c2: post-ReLU; b{i}.c3 / .ds: raw (pre-add); b{i}.out: after
+                  add + ReLU, against the join's output;
+      "pool":     mean((2, 3)) against the u8 average pool (the last block's
+                  qparams); "fc": the logits against the u8 logits.
+    No sync."""
+    from .qerror import _conv_deterministic
+    if batch < 1:
+        raise ValueError("layer_pairs: batch must be positive")
+    dev = qmodel.device
+    sp = qmodel.spec
+    with torch.cuda.device(dev), torch.no_grad():
+        def t(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        stem = [t(a) for a in folded["stem"]]
+        blocks = [{k: (t(v[0]), t(v[1]), v[2], v[3]) for k, v in b.items()} for b in folded["blocks"]]
+        fc = [t(a) for a in folded["fc"]]
+        for a in range(0, images.shape[0], batch):
+            xb = images[a:a + batch].to(dev)
+            x = normalized_input(xb, dev, qmodel.ntab).contiguous()
+            _, q = qmodel.run(xb.contiguous() if xb.dtype == torch.uint8 else x, keep="layers")
+            yield ("x", x, ops.quantize(x, qmodel.in_scale, qmodel.in_zp), qmodel.in_scale,
+                   qmodel.in_zp, True)
+            x = F.relu(_conv_deterministic(x, stem[0], stem[1], 2, 3))
+            yield "stem", x, q["stem.conv"], sp["stem"]["s_y"], sp["stem"]["z_y"], True
+            x = F.max_pool2d(x, 3, 2, 1)
+            for i, (b, e) in enumerate(zip(blocks, sp["blocks"])):
+                def cv(inp, k):
+                    w, bb, s, p = b[k]
+                    return _conv_deterministic(inp, w, bb, s, p)
+                y = F.relu(cv(x, "c1"))
+                yield f"b{i}.c1", y, q[f"block{i}.c1"], e["c1"]["s_y"], e["c1"]["z_y"], True
+                y = F.relu(cv(y, "c2"))
+                yield f"b{i}.c2", y, q[f"block{i}.c2"], e["c2"]["s_y"], e["c2"]["z_y"], True
+                y = cv(y, "c3")
+                yield f"b{i}.c3", y, q[f"block{i}.c3"], e["c3"]["s_y"], e["c3"]["z_y"], True
+                idn = x
+                if "ds" in b:
+                    idn = cv(x, "ds")
+                    yield f"b{i}.ds", idn, q[f"block{i}.ds"], e["ds"]["s_y"], e["ds"]["z_y"], True
+                x = F.relu(y + idn)
+                del y, idn
+                yield f"b{i}.out", x, q[f"block{i}"], e["out"][0], e["out"][1], True
+            last = sp["blocks"][-1]["out"] if sp["blocks"] else (sp["stem"]["s_y"], sp["stem"]["z_y"])
+            x = x.mean((2, 3))
+            yield "pool", x, q["pool"], last[0], last[1], True
+            x = F.linear(x, fc[0], fc[1])
+            yield "fc", x, q["fc.q"], sp["fc"]["s_y"], sp["fc"]["z_y"], True
+
+
+def layer_report(qmodel, folded, images, batch=32):
+    """{name: QuantErrorStats.result()} in layer_names order for ``images``
+    run through ``qmodel`` and its fp32 original (layer_pairs); one stats
+    object per name, one synchronisation, at the end."""
+    from .qerror import score_pairs
+    return score_pairs(layer_pairs(qmodel, folded, images, batch), qmodel.device)

@@ -35,7 +35,7 @@ import torch.nn.functional as F
 from . import ops
 from . import quant as Q
 from .data import IMAGENET_MEAN, IMAGENET_STD
-from .qmodel import _DevLayer, _Range, _weight_scale, cuda_device, normalized_input
+from .qmodel import _OBSERVERS, _DevLayer, _weight_scale, cuda_device, normalized_input
 
 F32 = np.float32
 
@@ -69,13 +69,20 @@ def unfolded_state(sd):
     return out
 
 
-def calibrate(net, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+def calibrate(net, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+              observer="minmax"):
     """The observers of the live-stub model: fp32 forward of the unfolded net
     (torch's own conv / batch_norm / pooling ops, as torch.ao's prepared model
     runs during calibration) recording, per int8 op, its QuantStub's input
     range ("<name>.in") and its output range ("<name>.out").  Batches:
     normalised fp32 NCHW, or raw uint8 NHWC images normalised here with
-    ``mean`` / ``std``."""
+    ``mean`` / ``std``.  observer="histogram": torch.ao's default
+    HistogramObserver (reduce_range=False) at the same points, the range its
+    searched clipping range (qmodel.calibrate); on device="cuda" it is
+    ops.HistogramObserver (qcn_histc_f32)."""
+    if observer not in _OBSERVERS:
+        raise ValueError(f"unknown observer {observer!r} (expected one of {sorted(_OBSERVERS)})")
+    make = _OBSERVERS[observer]
     dev = torch.device(device)
     ntab = Q.normalize_table(mean, std).to(dev)
 
@@ -86,7 +93,7 @@ def calibrate(net, batches, device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
 
     def obs(key, x):
         if key not in rng:
-            rng[key] = _Range(dev)
+            rng[key] = make(dev)
         rng[key](x)
 
     def qconv(name, x, layer):
@@ -139,11 +146,13 @@ def build_spec(net, ranges, per_channel=True):
 
 
 def quantize_resnet_reference(model, calib_batches, device="cuda", per_channel=True,
-                              calibration_device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD):
+                              calibration_device="cpu", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                              observer="minmax"):
     """fp32 ResNet (torchvision layout) -> QuantizedResNetQDQ on `device`.
-    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference)."""
+    ``mean`` / ``std`` normalise raw uint8 images (calibration and inference);
+    ``observer``: "minmax" or "histogram" (calibrate)."""
     net = unfolded_state(model.state_dict())
-    ranges = calibrate(net, calib_batches, calibration_device, mean, std)
+    ranges = calibrate(net, calib_batches, calibration_device, mean, std, observer)
     return QuantizedResNetQDQ(build_spec(net, ranges, per_channel), device, mean, std)
 
 
@@ -291,3 +300,94 @@ class QuantizedResNetQDQ:
     def cuda(self, device=None):
         self.host_io = False
         return self
+
+
+# ============================================================ error report
+def layer_names(qmodel):
+    """The hand-offs layer_pairs scores, in forward order."""
+    names = ["stem", "stem.pool"]
+    for i, b in enumerate(qmodel.blocks):
+        names += [f"b{i}.c1", f"b{i}.c2", f"b{i}.c3"]
+        names += ([f"b{i}.ds"] if b["ds"] is not None else []) + [f"b{i}"]
+    return names + ["pool", "fc"]
+
+
+def layer_pairs(qmodel, net, images, batch=32):
+    """Yield (name, x_fp32, y, scale, zero_point, nhwc) for every hand-off of
+    ``qmodel`` (a QuantizedResNetQDQ), batch by batch, in layer_names order
+    within a batch.  ``net``: unfolded_state of the fp32 model it was built
+    from; ``images``: fp32 NCHW, or raw uint8 NHWC (normalised with the model's
+    mean / std), host or device.
+
+    Per batch, on the model's device and current stream: ``qmodel.run(x,
+    keep=True)`` and the walk of calibrate() through torch ops (fp32 convs with
+    a deterministic algorithm), one layer's reference at a time.  ``y`` is u8
+    (scored with scale, zero_point) or fp32 NHWC (scale and zero_point None):
+      "stem", b{i}.c1|c2|c3|ds: the pre-BN conv output against the int8 conv's
+                   u8 output, with its own output qparams;
+      "stem.pool": fp32, after BN, ReLU and the max-pool, against the fp32
+                   block input; "b{i}": fp32, after the float-domain add and
+                   ReLU, against the fp32 block output; "pool": fp32 [N, C];
+      "fc":        the logits against the u8 logits.
+    No sync."""
+    from .qerror import _conv_deterministic
+    if batch < 1:
+        raise ValueError("layer_pairs: batch must be positive")
+    dev = qmodel.device
+    sp = qmodel.spec
+    with torch.cuda.device(dev), torch.no_grad():
+        def t(a):
+            return torch.from_numpy(np.ascontiguousarray(a, F32)).to(dev)
+
+        def up(layer):
+            w, st, pad, (m, v, g, b, eps) = layer
+            return t(w), st, pad, (t(m), t(v), t(g), t(b), eps)
+
+        stem = up(net["stem"])
+        blocks = [{k: up(v) for k, v in b.items()} for b in net["blocks"]]
+        fc = [t(a) for a in net["fc"]]
+
+        def conv(x, layer):
+            return _conv_deterministic(x, layer[0], None, layer[1], layer[2])
+
+        def bn(y, layer):
+            m, v, g, b, eps = layer[3]
+            return F.batch_norm(y, m, v, g, b, False, 0.0, eps)
+
+        for a in range(0, images.shape[0], batch):
+            xb = images[a:a + batch].to(dev)
+            x = normalized_input(xb, dev, qmodel.ntab).contiguous()
+            _, q = qmodel.run(xb.contiguous() if xb.dtype == torch.uint8 else x, keep=True)
+            y = conv(x, stem)
+            yield "stem", y, q["stem.q"], sp["stem"]["s_y"], sp["stem"]["z_y"], True
+            x = F.max_pool2d(F.relu(bn(y, stem)), 3, 2, 1).contiguous()
+            yield "stem.pool", x, q["stem"], None, None, True
+            for i, (b, e) in enumerate(zip(blocks, sp["blocks"])):
+                y = x
+                for k in ("c1", "c2", "c3"):
+                    y = conv(y, b[k])
+                    yield f"b{i}.{k}", y, q[f"block{i}.{k}"], e[k]["s_y"], e[k]["z_y"], True
+                    y = bn(y, b[k])
+                    if k != "c3":
+                        y = F.relu(y)
+                idn = x
+                if "ds" in b:
+                    idn = conv(x, b["ds"])
+                    yield f"b{i}.ds", idn, q[f"block{i}.ds"], e["ds"]["s_y"], e["ds"]["z_y"], True
+                    idn = bn(idn, b["ds"])
+                x = F.relu(y + idn).contiguous()
+                del y, idn
+                yield f"b{i}", x, q[f"block{i}"], None, None, True
+            x = torch.flatten(F.adaptive_avg_pool2d(x, 1), 1).contiguous()
+            yield "pool", x, q["pool"], None, None, True
+            x = F.linear(x, fc[0], fc[1])
+            yield "fc", x, q["fc.q"], sp["fc"]["s_y"], sp["fc"]["z_y"], True
+
+
+def layer_report(qmodel, net, images, batch=32):
+    """{name: result} in layer_names order for ``images`` run through
+    ``qmodel`` and its fp32 original (layer_pairs): QuantErrorStats.result()
+    for the u8 hand-offs, FloatErrorStats.result() for the fp32 ones; one
+    stats object per name, one synchronisation, at the end."""
+    from .qerror import score_pairs
+    return score_pairs(layer_pairs(qmodel, net, images, batch), qmodel.device)

@@ -167,6 +167,30 @@ int qcn_qerror_u8_f32(const float* x, const uint8_t* q, int n, int c, int h, int
                       float scale, int zero_point, long long* counts, double* sums,
                       void* workspace, void* stream);
 
+/* Error of an fp32 activation y against its fp32 reference x, per channel
+ * (the fp32 hand-offs of the reference-semantics ResNet: block outputs after
+ * the float-domain residual add, the pooled vector).
+ * x: fp32 NCHW [n,c,h,w] ([rows,c] is h = w = 1); y: fp32, NHWC when
+ * nhwc_y != 0 else NCHW.  Per element, IEEE with nothing contracted:
+ *   e = double(x) - double(y).
+ * int64 counts[c][3]: elements, #(x != y) (IEEE compare: -0.0 == +0.0), and
+ * the fp32 bit pattern of max fabsf(x - y), zero-extended.  double sums[c][4]:
+ * sum double(x)^2, sum e^2, sum |e|, sum e (signed: the channel's mean shift).
+ * NaN / +-inf are outside the contract.
+ * ADDS into counts and sums under qcn_qerror_u8_f32's rules: no floating-point
+ * atomics, per-workgroup partials in `workspace`
+ * (qcn_qerror_f32_workspace_size(n,c,h,w) bytes, 8-byte aligned, host
+ * arithmetic) added in a fixed order by a finishing launch, 64-bit integer
+ * atomics for counts; the same calls on one stream give the same bits;
+ * concurrent streams each need their own sums and workspace.  x and y need
+ * 4-byte alignment (16-byte loads where the pointer and the shape allow).
+ * 1 <= c <= 65536 and n*h*w < 2^31, else QCN_ERR_UNSUPPORTED; QCN_ERR_ARG for
+ * a null pointer, n < 0 or c / h / w < 1 — checked before any device call;
+ * n == 0 launches nothing. */
+long long qcn_qerror_f32_workspace_size(int n, int c, int h, int w);
+int qcn_qerror_f32_f32(const float* x, const float* y, int n, int c, int h, int w, int nhwc_y,
+                       long long* counts, double* sums, void* workspace, void* stream);
+
 /* Resize(R) -> CenterCrop(C) of raw u8 images of mixed sizes (the ImageNet
  * transform, utils/dataset_manager.py:24-25), byte for byte what Pillow's
  * bilinear Image.resize followed by a crop gives.
