@@ -2,7 +2,8 @@
 //  * static u8 x s8 -> u8 (QuantizedLinear / QuantizedLinearReLU, fbgemm),
 //    optional fused DeQuantStub (fp32 logits);
 //  * dynamic fp32 -> fp32 (quantized::linear_dynamic): device-side min/max,
-//    ChooseQuantizationParams, LEGACY quantize, GEMM, fp32 epilogue;
+//    ChooseQuantizationParams, LEGACY quantize, GEMM, fp32 epilogue; with the
+//    activation qparams of the whole batch (torch's) or of each row;
 //  * plain fp32 Linear (the fp32 fc2 of CustomQuantizedSimpleConvNet).
 //
 // GEMM shape: D[feature][row] = W[feature][k] * X[row][k]^T on
@@ -28,7 +29,11 @@ struct LinEpi {
   const float* dyn;       // device qparams: [scale, inv, zp(float), zp(int bits)]
 };
 
-template <bool DYN>
+// epilogue forms of the two GEMM kernels
+// (DYN_ROWS: ep.dyn holds one record per row)
+enum { EPI_STATIC = 0, EPI_DYN = 1, EPI_DYN_ROWS = 2 };
+
+template <int DYN>
 __global__ __launch_bounds__(256) void linear_u8s8_kernel(
     const uint8_t* __restrict__ x, int m, int k, int x_zp, const int8_t* __restrict__ w, int n,
     LinEpi ep, uint8_t* __restrict__ y, float* __restrict__ yf) {
@@ -102,8 +107,10 @@ __global__ __launch_bounds__(256) void linear_u8s8_kernel(
   int zx = x_zp;
   float s_x = 0.f;
   if constexpr (DYN) {
-    s_x = ep.dyn[0];
-    zx = __float_as_int(ep.dyn[3]);
+    // a lane's 32 outputs share its row, so the per-row form is two loads too
+    const float* dq = DYN == EPI_DYN_ROWS ? ep.dyn + 4 * (long)row : ep.dyn;
+    s_x = dq[0];
+    zx = __float_as_int(dq[3]);
   }
   const bool vec_ok = (n % 4) == 0;
 #pragma unroll
@@ -153,14 +160,14 @@ __global__ __launch_bounds__(256) void linear_u8s8_kernel(
 }
 
 // Generic fallback for K not a multiple of 128: one thread per output.
-template <bool DYN>
+template <int DYN>
 __global__ void linear_generic_kernel(const uint8_t* __restrict__ x, int m, int k, int x_zp,
                                       const int8_t* __restrict__ w, int n, LinEpi ep,
                                       uint8_t* __restrict__ y, float* __restrict__ yf) {
   const long total = (long)m * n;
   int zx = x_zp;
   float s_x = 0.f;
-  if constexpr (DYN) {
+  if constexpr (DYN == EPI_DYN) {
     s_x = ep.dyn[0];
     zx = __float_as_int(ep.dyn[3]);
   }
@@ -168,6 +175,10 @@ __global__ void linear_generic_kernel(const uint8_t* __restrict__ x, int m, int 
        e += (long)gridDim.x * blockDim.x) {
     const int f = (int)(e % n);
     const long row = e / n;
+    if constexpr (DYN == EPI_DYN_ROWS) {
+      s_x = ep.dyn[4 * row];
+      zx = __float_as_int(ep.dyn[4 * row + 3]);
+    }
     int acc = 0;
     for (int kk = 0; kk < k; ++kk) acc += ((int)x[row * k + kk] - zx) * (int)w[(long)f * k + kk];
     if constexpr (DYN) {
@@ -182,13 +193,12 @@ __global__ void linear_generic_kernel(const uint8_t* __restrict__ x, int m, int 
 }
 
 // ATen ChooseQuantizationParams (torch/include/ATen/native/quantized/cpu/
-// QuantUtils.h:70-185) on the device, preserve_sparsity = false,
-// force_scale_power_of_two = false.  dyn = [scale, inv, zp_f, zp_i(bits)].
-__global__ void choose_qparams_kernel(const float* __restrict__ mm, int reduce_range, float* dyn) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// QuantUtils.h:70-185), preserve_sparsity = false, force_scale_power_of_two =
+// false, from a [lo, hi] range.  Returns [scale, inv, zp_f, zp_i(bits)].
+__device__ __forceinline__ float4 choose_qparams(float lo, float hi, int reduce_range) {
   int qmin = 0, qmax = 255;
   if (reduce_range) { qmin = qmin / 2; qmax = qmax / 2; }
-  float mn = fminf(mm[0], 0.f), mx = fmaxf(mm[1], 0.f);
+  float mn = fminf(lo, 0.f), mx = fmaxf(hi, 0.f);
   double scale = ((double)mx - (double)mn) / (double)(qmax - qmin);
   if ((float)scale == 0.0f || __builtin_isinf(1.0f / (float)scale)) scale = 0.1;
   const float kSmall = 6.1e-5f;
@@ -213,23 +223,87 @@ __global__ void choose_qparams_kernel(const float* __restrict__ mm, int reduce_r
   else if (z0 > qmax) zp = qmax;
   else zp = (int)rint(z0);
   const float sf = (float)scale;
-  dyn[0] = sf;
-  dyn[1] = 1.0f / sf;
-  dyn[2] = (float)zp;
-  dyn[3] = __int_as_float(zp);
+  return make_float4(sf, 1.0f / sf, (float)zp, __int_as_float(zp));
+}
+
+// The per-batch form: mm = device [min, max], dyn = the record above.
+__global__ void choose_qparams_kernel(const float* __restrict__ mm, int reduce_range, float* dyn) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float4 r = choose_qparams(mm[0], mm[1], reduce_range);
+  dyn[0] = r.x;
+  dyn[1] = r.y;
+  dyn[2] = r.z;
+  dyn[3] = r.w;
 }
 
 // fbgemm::QuantizeAvx2<uint8_t, LEGACY=true>: q = clamp(rne(min(fmaf(x, inv, zp), 255)), 0, 255).
+__device__ __forceinline__ uint32_t quantize_legacy(float x, float inv, float zpf) {
+  float t = __builtin_fmaf(x, inv, zpf);
+  t = fminf(t, 255.0f);
+  t = __builtin_rintf(t);
+  t = fmaxf(t, 0.0f);
+  return (uint32_t)(int)t;
+}
+
 __global__ void quantize_legacy_kernel(const float* __restrict__ x, long long count,
                                        const float* __restrict__ dyn, uint8_t* __restrict__ q) {
   const float inv = dyn[1], zpf = dyn[2];
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < count;
-       i += (long long)gridDim.x * blockDim.x) {
-    float t = __builtin_fmaf(x[i], inv, zpf);
-    t = fminf(t, 255.0f);
-    t = __builtin_rintf(t);
-    t = fmaxf(t, 0.0f);
-    q[i] = (uint8_t)(int)t;
+       i += (long long)gridDim.x * blockDim.x)
+    q[i] = (uint8_t)quantize_legacy(x[i], inv, zpf);
+}
+
+// Per-row dynamic quantize: fp32 [m][k] -> u8 [m][k] and one record
+// [scale, inv, zp_f, zp_i(bits)] per row.  One wave per row, four rows per
+// workgroup, nothing shared between rows: pass 1 reduces the row's min/max by
+// xor shuffles, every lane then runs ChooseQuantizationParams on the reduced
+// pair (wave-uniform), pass 2 re-reads the row (16 KB at k = 4096, just
+// loaded by this wave) and quantizes it.  VEC (k % 4 == 0 and x 16-byte
+// aligned, so every row is): 16-byte loads, 4-byte stores; else scalar.
+template <bool VEC>
+__global__ __launch_bounds__(256) void quantize_rows_kernel(
+    const float* __restrict__ x, int m, int k, int reduce_range, float4* __restrict__ rec,
+    uint8_t* __restrict__ q) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= m) return;   // wave-uniform
+  const float* xr = x + row * k;
+  uint8_t* qr = q + row * k;
+  float lo = __builtin_inff(), hi = -__builtin_inff();
+  if constexpr (VEC) {
+    const float4* x4 = reinterpret_cast<const float4*>(xr);
+#pragma unroll 4
+    for (int c = lane; c < k / 4; c += 64) {
+      const float4 v = x4[c];
+      lo = fminf(lo, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
+      hi = fmaxf(hi, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
+    }
+  } else {
+#pragma unroll 4
+    for (int c = lane; c < k; c += 64) {
+      lo = fminf(lo, xr[c]);
+      hi = fmaxf(hi, xr[c]);
+    }
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, d));
+    hi = fmaxf(hi, __shfl_xor(hi, d));
+  }
+  const float4 r = choose_qparams(lo, hi, reduce_range);
+  if (lane == 0) rec[row] = r;
+  const float inv = r.y, zpf = r.z;
+  if constexpr (VEC) {
+    const float4* x4 = reinterpret_cast<const float4*>(xr);
+    uint32_t* q4 = reinterpret_cast<uint32_t*>(qr);
+#pragma unroll 4
+    for (int c = lane; c < k / 4; c += 64) {
+      const float4 v = x4[c];
+      q4[c] = quantize_legacy(v.x, inv, zpf) | (quantize_legacy(v.y, inv, zpf) << 8) |
+              (quantize_legacy(v.z, inv, zpf) << 16) | (quantize_legacy(v.w, inv, zpf) << 24);
+    }
+  } else {
+    for (int c = lane; c < k; c += 64) qr[c] = (uint8_t)quantize_legacy(xr[c], inv, zpf);
   }
 }
 
@@ -285,14 +359,14 @@ int qcn_linear_u8s8(const uint8_t* x, int m, int k, int x_zp, const int8_t* w, i
   hipStream_t st = (hipStream_t)stream;
   if (k % 128 == 0) {
     dim3 grid((n + 63) / 64, (m + 31) / 32);
-    hipLaunchKernelGGL(qcn::linear_u8s8_kernel<false>, grid, dim3(256), 0, st, x, m, k, x_zp, w, n,
-                       ep, y, y_deq);
+    hipLaunchKernelGGL(qcn::linear_u8s8_kernel<qcn::EPI_STATIC>, grid, dim3(256), 0, st, x, m, k,
+                       x_zp, w, n, ep, y, y_deq);
   } else {
     // generic path takes the raw zero point, not the (128 - zp) * wsum correction
     const long total = (long)m * n;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(qcn::linear_generic_kernel<false>, dim3(grid), dim3(256), 0, st, x, m, k,
-                       x_zp, w, n, ep, y, y_deq);
+    hipLaunchKernelGGL(qcn::linear_generic_kernel<qcn::EPI_STATIC>, dim3(grid), dim3(256), 0, st, x,
+                       m, k, x_zp, w, n, ep, y, y_deq);
   }
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
@@ -324,13 +398,13 @@ static int linear_dynamic_impl(const float* x, int m, int k, const int8_t* w, in
   qcn::LinEpi ep{nullptr, nullptr, nullptr, wsum, 0, 0, 0.f, w_scale, per_channel, bias, dyn};
   if (k % 128 == 0) {
     dim3 grid((n + 63) / 64, (m + 31) / 32);
-    hipLaunchKernelGGL(qcn::linear_u8s8_kernel<true>, grid, dim3(256), 0, st, qx, m, k, 0, w, n,
-                       ep, nullptr, y);
+    hipLaunchKernelGGL(qcn::linear_u8s8_kernel<qcn::EPI_DYN>, grid, dim3(256), 0, st, qx, m, k, 0,
+                       w, n, ep, nullptr, y);
   } else {
     const long total = (long)m * n;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    hipLaunchKernelGGL(qcn::linear_generic_kernel<true>, dim3(grid), dim3(256), 0, st, qx, m, k, 0,
-                       w, n, ep, nullptr, y);
+    hipLaunchKernelGGL(qcn::linear_generic_kernel<qcn::EPI_DYN>, dim3(grid), dim3(256), 0, st, qx,
+                       m, k, 0, w, n, ep, nullptr, y);
   }
   return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
@@ -350,6 +424,45 @@ int qcn_linear_dynamic_range_f32(const float* x, int m, int k, const int8_t* w, 
   if (!minmax) return QCN_ERR_ARG;
   return linear_dynamic_impl(x, m, k, w, n, w_scale, per_channel, wsum, bias, reduce_range,
                              minmax, y, workspace, stream);
+}
+
+// workspace: [m] row records of 16 bytes, then (at the next 64-byte boundary) the u8 activations
+static long long rows_q_offset(int m) { return (16LL * m + 63) / 64 * 64; }
+
+long long qcn_linear_dynamic_rows_workspace_size(int m, int k) {
+  return rows_q_offset(m) + (long long)m * k;
+}
+
+int qcn_linear_dynamic_rows_f32(const float* x, int m, int k, const int8_t* w, int n,
+                                const float* w_scale, int per_channel, const int32_t* wsum,
+                                const float* bias, int reduce_range, float* y, void* workspace,
+                                void* stream) {
+  if (!x || !w || !w_scale || !wsum || !y || !workspace) return QCN_ERR_ARG;
+  if (m <= 0 || k <= 0 || n <= 0) return QCN_ERR_ARG;
+  if ((uintptr_t)workspace % 16 != 0) return QCN_ERR_ARG;   // 16-byte records, 16-byte GEMM loads
+  hipStream_t st = (hipStream_t)stream;
+  float4* rec = reinterpret_cast<float4*>(workspace);
+  uint8_t* qx = reinterpret_cast<uint8_t*>(workspace) + rows_q_offset(m);
+  const dim3 qgrid((m + 3) / 4);
+  if (k % 4 == 0 && (uintptr_t)x % 16 == 0)
+    hipLaunchKernelGGL(qcn::quantize_rows_kernel<true>, qgrid, dim3(256), 0, st, x, m, k,
+                       reduce_range, rec, qx);
+  else
+    hipLaunchKernelGGL(qcn::quantize_rows_kernel<false>, qgrid, dim3(256), 0, st, x, m, k,
+                       reduce_range, rec, qx);
+  qcn::LinEpi ep{nullptr, nullptr, nullptr, wsum, 0, 0, 0.f, w_scale, per_channel, bias,
+                 reinterpret_cast<const float*>(rec)};
+  if (k % 128 == 0) {
+    dim3 grid((n + 63) / 64, (m + 31) / 32);
+    hipLaunchKernelGGL(qcn::linear_u8s8_kernel<qcn::EPI_DYN_ROWS>, grid, dim3(256), 0, st, qx, m, k, 0,
+                       w, n, ep, nullptr, y);
+  } else {
+    const long total = (long)m * n;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(qcn::linear_generic_kernel<qcn::EPI_DYN_ROWS>, dim3(grid), dim3(256), 0, st,
+                       qx, m, k, 0, w, n, ep, nullptr, y);
+  }
+  return hipGetLastError() == hipSuccess ? QCN_OK : QCN_ERR_HIP;
 }
 
 int qcn_linear_f32(const float* x, int m, int k, const float* w, int n, const float* b,

@@ -31,15 +31,32 @@ from qconvnet.data import CIFAR_MEAN, CIFAR_STD
 from qconvnet.qmodel import cuda_device, fold_state_dict, normalized_input
 
 F32 = np.float32
+GRANULARITIES = ("batch", "sample")
+
+
+def check_granularity(granularity):
+    if granularity not in GRANULARITIES:
+        raise ValueError(f"unknown granularity {granularity!r} (expected one of {GRANULARITIES})")
+    return granularity
 
 
 class DynamicQuantConvNet:
     """fp32 convs (+ optional BN fold) and dynamic-int8 fc1/fc2 on the GPU.
     Raw uint8 NHWC images are normalised with ``mean`` / ``std`` on the device
-    (ops.normalize_u8)."""
+    (ops.normalize_u8).
+
+    ``granularity``: whose min/max gives a dynamic Linear's activation qparams.
+    "batch" (default) is torch's quantize_dynamic: one range per call, so an
+    image's logits depend on the other images of its batch, and a batch split
+    over ranks needs the all-reduce of ``_range`` to stay batch-exact.
+    "sample": every row is quantized with its own range
+    (ops.linear_dynamic_rows): ``classify`` gives each row the result it
+    would get alone, at any batch size and in any shard, so no collective is
+    needed and ``sharded`` is not consulted."""
 
     def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
-                 std=CIFAR_STD):
+                 std=CIFAR_STD, granularity="batch"):
+        self.granularity = check_granularity(granularity)
         self.device = cuda_device(device)
         self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.reduce_range = reduce_range
@@ -102,19 +119,23 @@ class DynamicQuantConvNet:
                 x = F.max_pool2d(x, 2, 2)
         return x.reshape(x.shape[0], -1).contiguous()
 
+    def _linear(self, x, fc):
+        w, s, ws, b = fc
+        if self.granularity == "sample":
+            return ops.linear_dynamic_rows(x, w, s, ws, b, self.reduce_range)
+        return ops.linear_dynamic(x, w, s, ws, b, self.reduce_range, minmax=self._range(x))
+
     @torch.no_grad()
     def classify(self, feats):
         """dynamic-int8 fc1 -> [bn7] -> ReLU -> dynamic-int8 fc2 on [N, 4096]
         fp32 features (device tensor in, device logits out, no sync)."""
         with torch.cuda.device(self.device):
-            w, s, ws, b = self.fc[0]
-            x = ops.linear_dynamic(feats, w, s, ws, b, self.reduce_range, minmax=self._range(feats))
+            x = self._linear(feats, self.fc[0])
             if self.bn7 is not None:
                 x = ops.channel_affine(x, self.bn7[0], self.bn7[1], relu=True)
             else:
                 x = F.relu(x).contiguous()
-            w, s, ws, b = self.fc[1]
-            return ops.linear_dynamic(x, w, s, ws, b, self.reduce_range, minmax=self._range(x))
+            return self._linear(x, self.fc[1])
 
     def _forward(self, x):
         host = not x.is_cuda
@@ -174,12 +195,16 @@ class DynamicPTQModel:
     def __call__(self, x):
         return self.forward(x)
 
-    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD):
+    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD, granularity="batch"):
         """``mean`` / ``std``: the Normalize constants applied to raw uint8
-        NHWC images."""
+        NHWC images.  ``granularity``: "batch" (quantize_dynamic's per-call
+        activation range) or "sample" (one range per image: logits that do
+        not depend on the batch; see DynamicQuantConvNet)."""
+        check_granularity(granularity)
         self.fp32_model = self.fp32_model.cpu().eval()
         self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=True,
-                                                   device=self.device, mean=mean, std=std)
+                                                   device=self.device, mean=mean, std=std,
+                                                   granularity=granularity)
         return self.quantized_model
 
     def get_model_size(self):

@@ -33,6 +33,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from models.dynamic_ptq_model import check_granularity
 from models.resnet import resnet50
 from qconvnet import ops
 from qconvnet import quant as Q
@@ -42,9 +43,15 @@ from qconvnet.resnet import _fold, _np
 
 
 class DynamicFcResNet:
-    """Fused fp32 ResNet body on the GPU + dynamic int8 fc (HIP)."""
+    """Fused fp32 ResNet body on the GPU + dynamic int8 fc (HIP).
+    ``granularity``: "batch" (default, quantize_dynamic's one activation range
+    per call) or "sample" (the fc quantizes every row of features with its
+    own range, ops.linear_dynamic_rows: ``classify`` gives a row the same
+    logits at any batch size)."""
 
-    def __init__(self, model, device="cuda", reduce_range=True, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    def __init__(self, model, device="cuda", reduce_range=True, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                 granularity="batch"):
+        self.granularity = check_granularity(granularity)
         self.device = cuda_device(device)
         # raw uint8 NHWC images are normalised on the device (ops.normalize_u8)
         self.ntab = Q.normalize_table(mean, std).to(self.device)
@@ -96,6 +103,8 @@ class DynamicFcResNet:
         """Dynamic int8 fc on [N, 2048] fp32 features (device in, device out)."""
         with torch.cuda.device(self.device):
             w, s, ws, b = self.fc
+            if self.granularity == "sample":
+                return ops.linear_dynamic_rows(feats, w, s, ws, b, self.reduce_range)
             return ops.linear_dynamic(feats, w, s, ws, b, self.reduce_range)
 
     @torch.no_grad()
@@ -148,9 +157,12 @@ class OptimizedCustomQuantization:
         except _lib.QcnError as e:   # the reference raises when no engine exists (:17-22)
             raise RuntimeError("No supported quantization engine found: " + str(e)) from e
 
-    def quantize(self, model, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    def quantize(self, model, mean=IMAGENET_MEAN, std=IMAGENET_STD, granularity="batch"):
+        """``granularity``: "batch" or "sample" (see DynamicFcResNet)."""
+        check_granularity(granularity)
         model = model.cpu().eval()
-        self.quantized_model = DynamicFcResNet(model, self.device, mean=mean, std=std)
+        self.quantized_model = DynamicFcResNet(model, self.device, mean=mean, std=std,
+                                               granularity=granularity)
         return self.quantized_model
 
     def get_model_size(self, model):

@@ -39,19 +39,28 @@ class StaticPTQModel:
         self.fp32_model.load_state_dict(load_checkpoint_state(state_dict))
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
-                 max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD):
+                 max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD,
+                 granularity="batch"):
         """Calibrate (fp32, BN folded — the reference quantizes on the CPU, so
         does the default here) and build the int8 GPU model.  observer:
         "minmax" (default) or "histogram", torch.ao's default
         HistogramObserver (get_default_qconfig('fbgemm') activations,
         reduce_range=False).  ``mean`` / ``std``: the Normalize constants
         applied to raw uint8 NHWC images (calibration batches and inference
-        inputs may be either those or normalised fp32 NCHW)."""
+        inputs may be either those or normalised fp32 NCHW).  ``granularity``
+        ("batch" or "sample") belongs to mode="reference": whose range gives
+        the dynamic fc1/fc2 their activation qparams (DynamicQuantConvNet);
+        the static net has no dynamic layer, so "sample" is an error there."""
+        from models.dynamic_ptq_model import DynamicQuantConvNet, check_granularity
+        check_granularity(granularity)
+        if self.mode == "static" and granularity != "batch":
+            raise ValueError('granularity="sample" needs mode="reference": the static net has no '
+                             "dynamic layer")
         self.fp32_model.eval()
         if self.mode == "reference":
-            from models.dynamic_ptq_model import DynamicQuantConvNet
             self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=False,
-                                                       device=self.device, mean=mean, std=std)
+                                                       device=self.device, mean=mean, std=std,
+                                                       granularity=granularity)
             return self.quantized_model
         folded = fold_state_dict(self.fp32_model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)

@@ -137,6 +137,8 @@ SIGNATURES = {
     "qcn_linear_dynamic_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "qcn_linear_dynamic_range_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp,
                                            vp]),
+    "qcn_linear_dynamic_rows_workspace_size": (i64, [i32, i32]),
+    "qcn_linear_dynamic_rows_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "qcn_linear_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
 }
 

@@ -738,6 +738,30 @@ def linear_dynamic(x, w, w_scale, wsum, bias, reduce_range=True, workspace=None,
     return out
 
 
+def linear_dynamic_rows(x, w, w_scale, wsum, bias, reduce_range=True, workspace=None, out=None,
+                        qparams=False):
+    """The dynamic Linear with per-sample activation qparams: row i of the
+    result is ``linear_dynamic(x[i:i+1], ...)`` bit for bit, whatever else is
+    in the batch.  ``qparams=True`` also returns (scale [m] float32,
+    zero_point [m] int32) of the rows, copied out of the workspace."""
+    _need(x, torch.float32, "linear_dynamic_rows.x")
+    m, k = x.shape
+    n = w.shape[0]
+    if out is None:
+        out = torch.empty((m, n), dtype=torch.float32, device=x.device)
+    need = lib().qcn_linear_dynamic_rows_workspace_size(m, k)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    check(lib().qcn_linear_dynamic_rows_f32(_ptr(x), m, k, _ptr(w), n, _ptr(w_scale),
+                                            int(w_scale.numel() > 1), _ptr(wsum), _ptr(bias),
+                                            int(bool(reduce_range)), _ptr(out), _ptr(workspace),
+                                            _stream()), "linear_dynamic_rows")
+    if not qparams:
+        return out
+    rec = workspace[:16 * m].view(torch.float32).view(m, 4)   # [scale, 1/scale, zp, zp bits]
+    return out, (rec[:, 0].clone(), rec[:, 3].contiguous().view(torch.int32))
+
+
 def linear_f32(x, w, b, relu_in=False, out=None):
     _need(x, torch.float32, "linear_f32.x")
     m, k = x.shape

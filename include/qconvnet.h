@@ -488,6 +488,26 @@ int qcn_linear_dynamic_range_f32(const float* x, int m, int k, const int8_t* w, 
                                  const float* bias, int reduce_range, const float* minmax,
                                  float* y, void* workspace, void* stream);
 
+/* A8 with per-sample activation qparams: every row of x is quantized with the
+ * ChooseQuantizationParams of its own min/max, so row i of y is bit for bit
+ * qcn_linear_dynamic_f32 applied to x[i] alone ([1][k]) — an image's result
+ * does not depend on its batch, and a sharded batch needs no collective.
+ * Two launches (row min/max + qparams + quantize; GEMM with a per-row
+ * epilogue).  Other arguments as qcn_linear_dynamic_f32.  workspace: device
+ * memory, 16-byte aligned, qcn_linear_dynamic_rows_workspace_size(m, k) =
+ * roundup64(16 * m) + m * k bytes, laid out as
+ *   [0, 16 * m)                 one record per row: float scale, float 1/scale,
+ *                               float zero_point, int32 zero_point;
+ *   [roundup64(16 * m), + m*k)  the u8 activations, row-major;
+ * after the call a caller can read each row's scale and zero point there.
+ * NULL x, w, w_scale, wsum, y or workspace, or m, k or n <= 0: QCN_ERR_ARG,
+ * nothing launched. */
+long long qcn_linear_dynamic_rows_workspace_size(int m, int k);
+int qcn_linear_dynamic_rows_f32(const float* x, int m, int k, const int8_t* w, int n,
+                                const float* w_scale, int per_channel, const int32_t* wsum,
+                                const float* bias, int reduce_range, float* y, void* workspace,
+                                void* stream);
+
 /* fp32 Linear (fc2 of CustomQuantizedSimpleConvNet stays fp32,
  * custom_quantization_model.py:219): y = x @ w^T + b, with optional ReLU on x
  * (relu_in) applied on load. */
