@@ -1522,19 +1522,33 @@ struct Pix16 {
 };
 
 // One conv of the 16x16 pipeline over a staged patch: C::NCH K-steps of 32
-// MFMAs.  ga[s & 1] holds step s's four A fragments (step 0's issued by the
-// caller or by the previous job); step s + 1's are issued into the other slot
-// early in step s; after the last step the NEXT job's first chunk is issued
-// from wrn into slot 0 (its latency hides under the epilogue that follows).
-// B fragments are single-buffered: block j's fragment of step s + 1 is read
-// right after its fourth MFMA of step s.  lb: this lane's patch byte offset
-// (Pix16<C>::at(wp, 0, p) + 16 g); voff: ((wc 64 + p) 64 + 16 g).
+// MFMAs, cout block i outermost (m = 8 i + j).  ga[s & 1] holds step s's four
+// A fragments.  Fragment i of step s is dead after its block's eight MFMAs,
+// and step s + 2's fragment i is issued into the same registers right there:
+// a weight fragment is requested 56 MFMAs before its first use and needs no
+// third slot.  Step 0's chunk is in flight on entry (issued by the caller or
+// by the previous job, under the epilogue in between); step 1's is issued on
+// entry, 32 MFMAs ahead; after the last step the NEXT job's first chunk is
+// issued from wrn into slot 0.  (Refilling the last two steps' registers with
+// the next job's steps 0 and 1 holds 32 more VGPRs across the epilogue: the
+// one launch then spills 26-41 VGPRs, with step 0 alone 8.)  All eight B
+// fragments are live for the whole step: block j's fragment of step s + 1 is
+// read in the i == 3 pass, right after its last MFMA of step s, 8 MFMAs
+// ahead.  lb: this lane's patch byte offset (Pix16<C>::at(wp, 0, p) + 16 g);
+// voff: ((wc 64 + p) 64 + 16 g).
+template <class C>
+QCN_DEV void ga_issue16(v4i (&ga)[2][4], wt_rsrc_t r, int voff, int s, int slot, int i) {
+  const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, s * C::WBUF + i * 1024, 0);
+  ga[slot][i] = (v4i){(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
+}
+
 template <class C>
 QCN_DEV void pipe_job16(const uint8_t* patch, const int* corr, wt_rsrc_t wr, wt_rsrc_t wrn, int voff, int wc,
                         int lb, int g, v4i (&acc)[4][8], v4i (&ga)[2][4]) {
   constexpr int CBK = C::kCin / 64, S = C::NCH;
   using X = Pix16<C>;
   static_assert(X::affine(), "pixel blocks at constant offsets");
+  static_assert(S >= 3, "steps s and s + 1 in flight while s + 2 is requested");
   v4i c0[4];   // the first K-step's C operand: the zero-point correction
 #pragma unroll
   for (int i = 0; i < 4; ++i) c0[i] = *reinterpret_cast<const v4i*>(corr + wc * 64 + 16 * i + 4 * g);
@@ -1542,26 +1556,21 @@ QCN_DEV void pipe_job16(const uint8_t* patch, const int* corr, wt_rsrc_t wr, wt_
     const int tap = s / CBK, cb = s % CBK;
     return *reinterpret_cast<const v4i*>(patch + lb + X::jofs(j) + PatchAddr<C>::delta(tap, j) + cb * 64);
   };
-  auto issue = [&](wt_rsrc_t r, int s, int slot) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, s * C::WBUF + i * 1024, 0);
-      ga[slot][i] = (v4i){(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
-    }
-  };
+  for (int i = 0; i < 4; ++i) ga_issue16<C>(ga, wr, voff, 1, 1, i);
   v4i fb[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) fb[j] = rd_b(0, j);
   static_for<S>([&](auto sc) {
     constexpr int s = decltype(sc)::value;
     static_for<32>([&](auto mc) {
-      constexpr int m = decltype(mc)::value, j = m >> 2, i = m & 3;
+      constexpr int m = decltype(mc)::value, i = m >> 3, j = m & 7;
       __builtin_amdgcn_sched_barrier(0);
       acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ga[s & 1][i], fb[j], s == 0 ? c0[i] : acc[i][j], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (m == 1 && s + 1 < S) {
-        // slot (s + 1) & 1 was step s - 1's: all its MFMAs have issued
-        issue(wr, s + 1, (s + 1) & 1);
+      if constexpr (j == 7) {
+        // block i's fragment is dead: its registers take step s + 2's
+        if constexpr (s + 2 < S) ga_issue16<C>(ga, wr, voff, s + 2, s & 1, i);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (i == 3 && s + 1 < S) {
@@ -1576,7 +1585,8 @@ QCN_DEV void pipe_job16(const uint8_t* patch, const int* corr, wt_rsrc_t wr, wt_
 #pragma unroll
       for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(acc[i][j]));
   });
-  issue(wrn, 0, 0);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ga_issue16<C>(ga, wrn, voff, 0, 0, i);
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -1620,7 +1630,9 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   const int tid = threadIdx.x;
   const int role = __builtin_amdgcn_readfirstlane(tid >> 8);   // 0: conv A, 1: conv B
-  const int rt = tid & 255, lane = tid & 63, wave = rt >> 6;   // thread / wave within the role
+  const int rt = tid & 255, lane = tid & 63;   // thread within the role
+  // wave within the role, uniform: what derives from it alone stays in SGPRs
+  const int wave = __builtin_amdgcn_readfirstlane(rt >> 6);
   const int wc = wave % WCO, wp = wave / WCO;
   int T;
   if constexpr (ILV) {
@@ -1638,12 +1650,12 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
     const int n = ILV ? b + (k * SEGS + sg) * G : (b + k * G) * SEGS + sg;
     return n < nimg ? n : (ILV ? b + k * SEGS * G : (b + k * G) * SEGS);
   };
-  auto in_src = [&](int k, int q) {
+  auto in_src = [&](int k, int q, int rt) {
     const int p = rt + 256 * q;
     const int n = img_of(k, p / (IMG * CH16));
     return x + ((long)n * IMG + (p / CH16) % IMG) * CA::kCin + (p % CH16) * 16;
   };
-  auto in_dst = [&](int q) {
+  auto in_dst = [&](int q, int rt) {
     const int p = rt + 256 * q;
     const int pix = (p / CH16) % IMG;
     return CA::slot(p / (IMG * CH16), pix / W + 1, pix % W + 1) + (p % CH16) * 16;
@@ -1654,7 +1666,7 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
   uint4 sv0[4];
   if (role == 0 && T > 0) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) sv0[q] = *reinterpret_cast<const uint4*>(in_src(0, q));
+    for (int q = 0; q < 4; ++q) sv0[q] = *reinterpret_cast<const uint4*>(in_src(0, q, rt));
   }
   float* eka = reinterpret_cast<float*>(lds + P::OFF_EA);
   float* ekb = reinterpret_cast<float*>(lds + P::OFF_EB);
@@ -1718,22 +1730,27 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
   const int p16 = lane & 15, g = lane >> 4;
   const wt_rsrc_t wra = wt_rsrc(wa), wrb = wt_rsrc(wb);
   const int voff = (wc * 64 + p16) * 64 + g * 16;
+  // this thread's index within its role from a laundered id: the staging
+  // addresses are computed where they are used, not held across the MFMA jobs
+  auto fresh_rt = [&]() {
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    return t & 255;
+  };
   auto pa_buf = [&](int j) { return lds + P::OFF_PA + (P::DOUBLE_A ? (j & 1) * P::PA : 0); };
   auto pb_buf = [&](int j) { return lds + P::OFF_PB + (j & 1) * P::PB; };
   auto write_in = [&](uint8_t* pa, const uint4 (&sv)[4]) {
+    const int rz = fresh_rt();
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      *reinterpret_cast<uint4*>(pa + in_dst(q)) =
+      *reinterpret_cast<uint4*>(pa + in_dst(q, rz)) =
           make_uint4(xor80(sv[q].x), xor80(sv[q].y), xor80(sv[q].z), xor80(sv[q].w));
   };
   // each role's first weight chunk, issued inside its own branch (the B
   // waves' first job starts a period later, the A waves' at once)
-  auto first_chunk = [&](wt_rsrc_t w0, v4i (&ga)[2][4]) {
+  auto first_chunk = [&](auto cfg, wt_rsrc_t w0, v4i (&ga)[2][4]) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const auto v = __builtin_amdgcn_raw_buffer_load_b128(w0, voff, i * 1024, 0);
-      ga[0][i] = (v4i){(int)v[0], (int)v[1], (int)v[2], (int)v[3]};
-    }
+    for (int i = 0; i < 4; ++i) ga_issue16<decltype(cfg)>(ga, w0, voff, 0, 0, i);
   };
 
   v4i acc[4][8];
@@ -1766,7 +1783,9 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
   };
   // A's epilogue into B's patch pb: one dword (4 channels) per block and row
   // of 16 channels, at the block's constant offset
-  auto epi_a = [&](const Lane& L, uint8_t* pb) {
+  // (after_first runs once cout block 0's accumulators are dead: the A role
+  // loads its next input there, where the registers for it are free)
+  auto epi_a = [&](const Lane& L, uint8_t* pb, auto&& after_first) {
     static_for<4>([&](auto ic) {
       constexpr int i = decltype(ic)::value;
       const EpiG K = load_epig(eka, CA::kCout, L.ek + 16 * i);
@@ -1777,6 +1796,11 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
         for (int r = 0; r < 4; ++r) wd = rq_elem<FA>(acc[i][j][r], K, r, epa, wd);
         *reinterpret_cast<uint32_t*>(pb + L.hb + XA::template out_jofs<CB>(j) + 16 * i) = xor80(wd);
       });
+      if constexpr (i == 0) {
+        __builtin_amdgcn_sched_barrier(0);
+        after_first();
+        __builtin_amdgcn_sched_barrier(0);
+      }
     });
   };
   // B's pooled epilogue of tile k: per group of 16 pooled pixels, the max over
@@ -1820,7 +1844,7 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
 
   if (role == 0) {
     v4i ga[2][4];
-    first_chunk(wra, ga);
+    first_chunk(CA{}, wra, ga);
     uint4 sv[4] = {};   // tile p + 1's input, loaded during period p
 #pragma unroll 1
     for (int p = 0; p <= T; ++p) {
@@ -1833,10 +1857,13 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
         const Lane L = lanes();
         pipe_job16<CA>(pa_buf(p), L.ca, wra, wra, voff, wc, L.la, L.g, acc, ga);
         WS16_STAMP(p, 1);
-        const int kn = p + 1 < T ? p + 1 : p;
+        // the next tile's input is requested inside the epilogue (before it,
+        // beside all of acc, the staged values were spilled)
+        epi_a(L, pb_buf(p), [&]() {
+          const int kn = p + 1 < T ? p + 1 : p, rz = fresh_rt();
 #pragma unroll
-        for (int q = 0; q < 4; ++q) sv[q] = *reinterpret_cast<const uint4*>(in_src(kn, q));
-        epi_a(L, pb_buf(p));
+          for (int q = 0; q < 4; ++q) sv[q] = *reinterpret_cast<const uint4*>(in_src(kn, q, rz));
+        });
         if constexpr (P::DOUBLE_A) write_in(pa_buf(p + 1), sv);
         WS16_STAMP(p, 2);
       }
@@ -1844,7 +1871,7 @@ QCN_DEV void convpair_ws16_body(int b, int G, const uint8_t* __restrict__ x, int
     }
   } else {
     v4i ga[2][4];
-    first_chunk(wrb, ga);
+    first_chunk(CB{}, wrb, ga);
 #pragma unroll 1
     for (int p = 0; p <= T; ++p) {
       if constexpr (!P::DOUBLE_A) lds_barrier();
