@@ -10,9 +10,10 @@ MI355X version: fc1 and fc2 run ``quantized::linear_dynamic`` semantics in the
 HIP kernel (device-side min/max -> ChooseQuantizationParams with reduce_range
 -> LEGACY quantize -> u8 x s8 MFMA GEMM -> y = fmaf(acc, s_x*s_w, b)), bit-exact
 with FBGEMM for the same fp32 input.  The six fp32 convolutions are the
-reference's fp32 ops and run through torch (MIOpen) on the same device — an
-fp32 conv is outside this path's int8 scope (SURVEY §8(f) row 1 lists the
-batch-exact dynamic path as the next step).  The ResNet-50
+reference's fp32 ops: through torch (MIOpen) on the same device by default
+(``body="torch"``), or through the deterministic HIP kernel of
+csrc/conv_f32.hip (``body="hip"``), which makes the features, and
+with ``granularity="sample"`` the logits, independent of the batch.  The ResNet-50
 ``CustomDynamicQuantization`` of :13-216 needs torchvision and a weight
 download and is out of scope.
 """
@@ -32,12 +33,19 @@ from qconvnet.qmodel import cuda_device, fold_state_dict, normalized_input
 
 F32 = np.float32
 GRANULARITIES = ("batch", "sample")
+BODIES = ("torch", "hip")
 
 
 def check_granularity(granularity):
     if granularity not in GRANULARITIES:
         raise ValueError(f"unknown granularity {granularity!r} (expected one of {GRANULARITIES})")
     return granularity
+
+
+def check_body(body):
+    if body not in BODIES:
+        raise ValueError(f"unknown body {body!r} (expected one of {BODIES})")
+    return body
 
 
 class DynamicQuantConvNet:
@@ -52,11 +60,19 @@ class DynamicQuantConvNet:
     "sample": every row is quantized with its own range
     (ops.linear_dynamic_rows): ``classify`` gives each row the result it
     would get alone, at any batch size and in any shard, so no collective is
-    needed and ``sharded`` is not consulted."""
+    needed and ``sharded`` is not consulted.
+
+    ``body``: who runs the six fp32 convolutions of ``features``.  "torch"
+    (default) is F.conv2d, i.e. MIOpen, whose algorithm and summation order may
+    differ per batch size.  "hip" is ops.conv3x3_f32, six launches with BN,
+    ReLU and the pools in their epilogues and a summation order fixed by the
+    kernel: an image's features are the same bits in any batch, so with
+    granularity="sample" the logits are too, images in to logits out."""
 
     def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
-                 std=CIFAR_STD, granularity="batch"):
+                 std=CIFAR_STD, granularity="batch", body="torch"):
         self.granularity = check_granularity(granularity)
+        self.body = check_body(body)
         self.device = cuda_device(device)
         self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.reduce_range = reduce_range
@@ -79,6 +95,12 @@ class DynamicQuantConvNet:
                 *(g[f"bn7.{k}"] for k in ("running_mean", "running_var", "weight", "bias"))))
         self.convs = [(self._t(w), self._t(b), tuple(self._t(a) for a in bn) if bn else None)
                       for w, b, bn in convs]
+        self.packed = None
+        if self.body == "hip":
+            # (packed weights, bias, BN as fma(x, alpha, beta) or None) per conv
+            self.packed = [(self._t(ops.pack_conv3x3_f32(w)), self._t(b),
+                            tuple(self._t(a) for a in Q.bn_eval_affine(*bn)) if bn else None)
+                           for w, b, bn in convs]
         self.fc = []
         for w, b in ((fc1w, fc1b), (g["fc2.weight"], g["fc2.bias"])):
             s_w = Q.qparams_symmetric(w.min(), w.max())     # default_weight_observer
@@ -110,6 +132,8 @@ class DynamicQuantConvNet:
 
     def features(self, x):
         """fp32 convs (+BN, ReLU, pools) -> the [N, 4096] NCHW-flatten fc1 input."""
+        if self.body == "hip":
+            return self._features_hip(x)
         for i, (w, b, bn) in enumerate(self.convs):
             x = F.conv2d(x, w, b, padding=1)
             if bn is not None:
@@ -118,6 +142,15 @@ class DynamicQuantConvNet:
             if CONV_TABLE[i][2]:
                 x = F.max_pool2d(x, 2, 2)
         return x.reshape(x.shape[0], -1).contiguous()
+
+    def _features_hip(self, x):
+        """NCHW in at conv1, NHWC between the layers, NCHW-flatten out of conv6."""
+        x = x.contiguous()
+        last = len(self.packed) - 1
+        for i, (wp, b, affine) in enumerate(self.packed):
+            x = ops.conv3x3_f32(x, wp, CONV_TABLE[i][1], bias=b, affine=affine, relu=True,
+                                pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0, y_nchw=i == last)
+        return x.reshape(x.shape[0], -1)
 
     def _linear(self, x, fc):
         w, s, ws, b = fc
@@ -195,16 +228,19 @@ class DynamicPTQModel:
     def __call__(self, x):
         return self.forward(x)
 
-    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD, granularity="batch"):
+    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD, granularity="batch", body="torch"):
         """``mean`` / ``std``: the Normalize constants applied to raw uint8
         NHWC images.  ``granularity``: "batch" (quantize_dynamic's per-call
-        activation range) or "sample" (one range per image: logits that do
-        not depend on the batch; see DynamicQuantConvNet)."""
+        activation range) or "sample" (one range per image).  ``body``:
+        "torch" (MIOpen convolutions) or "hip" (ops.conv3x3_f32); with
+        "sample" and "hip" an image's logits are bit-identical whatever batch
+        it arrives in (see DynamicQuantConvNet)."""
         check_granularity(granularity)
+        check_body(body)
         self.fp32_model = self.fp32_model.cpu().eval()
         self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=True,
                                                    device=self.device, mean=mean, std=std,
-                                                   granularity=granularity)
+                                                   granularity=granularity, body=body)
         return self.quantized_model
 
     def get_model_size(self):

@@ -40,7 +40,7 @@ class StaticPTQModel:
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
                  max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD,
-                 granularity="batch"):
+                 granularity="batch", body="torch"):
         """Calibrate (fp32, BN folded — the reference quantizes on the CPU, so
         does the default here) and build the int8 GPU model.  observer:
         "minmax" (default) or "histogram", torch.ao's default
@@ -50,9 +50,14 @@ class StaticPTQModel:
         inputs may be either those or normalised fp32 NCHW).  ``granularity``
         ("batch" or "sample") belongs to mode="reference": whose range gives
         the dynamic fc1/fc2 their activation qparams (DynamicQuantConvNet);
-        the static net has no dynamic layer, so "sample" is an error there."""
-        from models.dynamic_ptq_model import DynamicQuantConvNet, check_granularity
+        the static net has no dynamic layer, so "sample" is an error there.
+        ``body`` ("torch" or "hip") belongs to mode="reference" too: who runs
+        its fp32 convolutions; the static net has none, so "hip" is an error."""
+        from models.dynamic_ptq_model import DynamicQuantConvNet, check_body, check_granularity
         check_granularity(granularity)
+        check_body(body)
+        if self.mode == "static" and body != "torch":
+            raise ValueError('body="hip" needs mode="reference": the static net has no fp32 conv')
         if self.mode == "static" and granularity != "batch":
             raise ValueError('granularity="sample" needs mode="reference": the static net has no '
                              "dynamic layer")
@@ -60,7 +65,7 @@ class StaticPTQModel:
         if self.mode == "reference":
             self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=False,
                                                        device=self.device, mean=mean, std=std,
-                                                       granularity=granularity)
+                                                       granularity=granularity, body=body)
             return self.quantized_model
         folded = fold_state_dict(self.fp32_model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)

@@ -140,6 +140,9 @@ SIGNATURES = {
     "qcn_linear_dynamic_rows_workspace_size": (i64, [i32, i32]),
     "qcn_linear_dynamic_rows_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp]),
     "qcn_linear_f32": (i32, [vp, i32, i32, vp, i32, vp, i32, vp, vp]),
+    "qcn_conv3x3_f32_packed_size": (i32, [i32, i32]),
+    "qcn_pack_conv3x3_weight_f32": (i32, [vp, i32, i32, vp]),
+    "qcn_conv3x3_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]),
 }
 
 _lib = None

@@ -773,6 +773,54 @@ def linear_f32(x, w, b, relu_in=False, out=None):
     return out
 
 
+# ------------------------------------------- deterministic fp32 conv
+def pack_conv3x3_f32(w):
+    """Host packing of fp32 OIHW [cout, cin, 3, 3] weights (numpy array or
+    tensor) for ``conv3x3_f32``: a float32 numpy array in the kernel's operand
+    order (include/qconvnet.h)."""
+    if torch.is_tensor(w):
+        w = w.detach().cpu().numpy()
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise ValueError(f"pack_conv3x3_f32: expected [cout, cin, 3, 3], got {w.shape}")
+    cout, cin = w.shape[:2]
+    size = lib().qcn_conv3x3_f32_packed_size(cin, cout)
+    if size < 0:
+        check(size, "conv3x3_f32_packed_size")
+    out = np.empty(size, np.float32)
+    check(lib().qcn_pack_conv3x3_weight_f32(w.ctypes.data, cout, cin, out.ctypes.data),
+          "pack_conv3x3_f32")
+    return out
+
+
+def conv3x3_f32(x, packed, cout, bias=None, affine=None, relu=False, pool=False, x_nchw=False,
+                y_nchw=False, out=None):
+    """3x3 / stride 1 / padding 1 fp32 convolution with a summation order fixed
+    by the kernel: image i of the result does not depend on the rest of the
+    batch.  ``x``: NHWC [n, h, w, cin] (NCHW [n, cin, h, w] with ``x_nchw``);
+    ``packed``: device tensor of ``pack_conv3x3_f32``; ``affine``: (alpha, beta)
+    per channel, applied as fma(t, alpha, beta) after the bias; then ReLU, then
+    the 2x2 max pool.  Returns NHWC (NCHW with ``y_nchw``)."""
+    _need(x, torch.float32, "conv3x3_f32.x")
+    _need(packed, torch.float32, "conv3x3_f32.packed")
+    if x_nchw:
+        n, cin, h, w = x.shape
+    else:
+        n, h, w, cin = x.shape
+    if packed.numel() != lib().qcn_conv3x3_f32_packed_size(cin, cout):
+        raise ValueError("conv3x3_f32.packed: size does not match (cin, cout)")
+    oh, ow = (h // 2, w // 2) if pool else (h, w)
+    if out is None:
+        out = torch.empty((n, cout, oh, ow) if y_nchw else (n, oh, ow, cout), dtype=torch.float32,
+                          device=x.device)
+    alpha, beta = affine if affine is not None else (None, None)
+    check(lib().qcn_conv3x3_f32(_ptr(x), n, h, w, cin, int(bool(x_nchw)), _ptr(packed), cout,
+                                _ptr(bias), _ptr(alpha), _ptr(beta), int(bool(relu)),
+                                int(bool(pool)), int(bool(y_nchw)), _ptr(out), _stream()),
+          "conv3x3_f32")
+    return out
+
+
 # ------------------------------------------------ SURVEY §8(f)2: ResNet blocks
 def pack_conv_kmajor(w_oihw: np.ndarray):
     """s8 OIHW -> (chunk-major [kh*kw*cin/32, cout, 32] bytes, wsum int32)."""

@@ -676,6 +676,33 @@ int qcn_qdq_join_f32(const uint8_t* y3, float s3, int z3, const float* a3, const
  * the host's vector width and is not reproduced. */
 int qcn_avgpool_f32_nhwc(const float* x, int n, int h, int w, int c, float* out, void* stream);
 
+/* ---- deterministic fp32 3x3 conv -----------------------------
+ * 3x3, stride 1, padding 1, fp32 in / out on v_mfma_f32_32x32x2_f32; the
+ * summation order of an output element is fixed by the kernel and does not
+ * depend on nimg, so an image's result is the same bits in any batch.  K runs
+ * over Cin chunks of 64 ascending, inside a chunk tap-major (ky, kx) and
+ * channel-minor; one fp32 accumulator chain from +0 per output.  NaN, inf and
+ * denormal inputs are outside the contract. */
+/* Floats of the packed weights (negative: a status). */
+int qcn_conv3x3_f32_packed_size(int cin, int cout);
+/* Host packing of OIHW fp32 weights into the MFMA B-operand lane order.  With
+ * ng = ceil(cin / 8) channel groups and 2 * ceil(cout / 64) column tiles ct:
+ *   out[((ct * 9 * ng + step) * 64 + lane) * 4 + s]
+ *     = w[32 ct + lane % 32][8 G + 2 s + lane / 32][tap]
+ * step = 72 * (G / 8) + tap * gc + G % 8, gc = min(8, ng - 8 * (G / 8)) the
+ * groups of G's chunk, tap = 3 ky + kx; +0 where the channel is past cin or
+ * the column past cout. */
+int qcn_pack_conv3x3_weight_f32(const float* w_oihw, int cout, int cin, float* out);
+/* y = [pool2x2] [relu] [fmaf(., alpha[c], beta[c])] (conv(x, w) [+ bias[c]]).
+ * x: NHWC [nimg][h][w][cin], or torch's NCHW with x_nchw; y: NHWC, or NCHW
+ * with y_nchw, [h/2][w/2] maps with pool (h and w even).  bias, alpha, beta
+ * may be NULL, alpha and beta only together.  w_packed 16-byte aligned.
+ * QCN_ERR_ARG for bad pointers and sizes, QCN_ERR_UNSUPPORTED when x or y has
+ * more than 2^31 - 1 elements; both before any launch. */
+int qcn_conv3x3_f32(const float* x, int nimg, int h, int w, int cin, int x_nchw,
+                    const float* w_packed, int cout, const float* bias, const float* alpha,
+                    const float* beta, int relu, int pool, int y_nchw, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
