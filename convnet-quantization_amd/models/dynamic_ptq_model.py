@@ -13,7 +13,11 @@ with FBGEMM for the same fp32 input.  The six fp32 convolutions are the
 reference's fp32 ops: through torch (MIOpen) on the same device by default
 (``body="torch"``), or through the deterministic HIP kernel of
 csrc/conv_f32.hip (``body="hip"``), which makes the features, and
-with ``granularity="sample"`` the logits, independent of the batch.  The ResNet-50
+with ``granularity="sample"`` the logits, independent of the batch.
+``body="int8"`` goes past the reference: the six convolutions are
+dynamically quantized too, every image by its own range, on the int8 MFMA
+(csrc/conv_dyn.hip); nothing is calibrated and the batch independence holds
+by integer arithmetic.  The ResNet-50
 ``CustomDynamicQuantization`` of :13-216 needs torchvision and a weight
 download and is out of scope.
 """
@@ -33,7 +37,7 @@ from qconvnet.qmodel import cuda_device, fold_state_dict, normalized_input
 
 F32 = np.float32
 GRANULARITIES = ("batch", "sample")
-BODIES = ("torch", "hip")
+BODIES = ("torch", "hip", "int8")
 
 
 def check_granularity(granularity):
@@ -67,10 +71,16 @@ class DynamicQuantConvNet:
     differ per batch size.  "hip" is ops.conv3x3_f32, six launches with BN,
     ReLU and the pools in their epilogues and a summation order fixed by the
     kernel: an image's features are the same bits in any batch, so with
-    granularity="sample" the logits are too, images in to logits out."""
+    granularity="sample" the logits are too, images in to logits out.
+    "int8" is ops.conv3x3_dyn: the conv weights are quantized once (symmetric
+    s8, per output channel unless ``conv_per_channel=False``), every layer
+    quantizes each image's activations with the qparams of that image's own
+    min/max (full 8 bits: ``reduce_range`` applies to the Linears only) and
+    accumulates in int32, so the same invariance holds and the convolutions are
+    no longer the reference's fp32 ops."""
 
     def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
-                 std=CIFAR_STD, granularity="batch", body="torch"):
+                 std=CIFAR_STD, granularity="batch", body="torch", conv_per_channel=True):
         self.granularity = check_granularity(granularity)
         self.body = check_body(body)
         self.device = cuda_device(device)
@@ -101,6 +111,17 @@ class DynamicQuantConvNet:
             self.packed = [(self._t(ops.pack_conv3x3_f32(w)), self._t(b),
                             tuple(self._t(a) for a in Q.bn_eval_affine(*bn)) if bn else None)
                            for w, b, bn in convs]
+        self.qconvs = None
+        if self.body == "int8":
+            # (packed s8 weights, wsum, s_w, bias, BN as fma(x, alpha, beta) or None) per conv
+            self.qconvs = []
+            for w, b, bn in convs:
+                flat = w.reshape(w.shape[0], -1)
+                s_w = (Q.qparams_symmetric(flat.min(1), flat.max(1)) if conv_per_channel
+                       else np.atleast_1d(Q.qparams_symmetric(w.min(), w.max())))
+                wp, wsum = ops.pack_conv3x3_dyn(Q.quantize_weight(w, s_w))
+                self.qconvs.append((self._t(wp), self._t(wsum), self._t(s_w), self._t(b),
+                                    tuple(self._t(a) for a in Q.bn_eval_affine(*bn)) if bn else None))
         self.fc = []
         for w, b in ((fc1w, fc1b), (g["fc2.weight"], g["fc2.bias"])):
             s_w = Q.qparams_symmetric(w.min(), w.max())     # default_weight_observer
@@ -134,6 +155,8 @@ class DynamicQuantConvNet:
         """fp32 convs (+BN, ReLU, pools) -> the [N, 4096] NCHW-flatten fc1 input."""
         if self.body == "hip":
             return self._features_hip(x)
+        if self.body == "int8":
+            return self._features_int8(x)
         for i, (w, b, bn) in enumerate(self.convs):
             x = F.conv2d(x, w, b, padding=1)
             if bn is not None:
@@ -150,6 +173,19 @@ class DynamicQuantConvNet:
         for i, (wp, b, affine) in enumerate(self.packed):
             x = ops.conv3x3_f32(x, wp, CONV_TABLE[i][1], bias=b, affine=affine, relu=True,
                                 pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0, y_nchw=i == last)
+        return x.reshape(x.shape[0], -1)
+
+    def _features_int8(self, x):
+        """One per-image min/max launch, then six dynamic int8 convs, each
+        handing its output's per-image range to the next (layouts as
+        _features_hip)."""
+        x = x.contiguous()
+        stats = ops.image_minmax(x)
+        last = len(self.qconvs) - 1
+        for i, (wp, wsum, s_w, b, affine) in enumerate(self.qconvs):
+            x, stats = ops.conv3x3_dyn(x, stats, wp, wsum, s_w, CONV_TABLE[i][1], bias=b, affine=affine,
+                                       relu=True, pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0,
+                                       y_nchw=i == last, want_stats=i != last)
         return x.reshape(x.shape[0], -1)
 
     def _linear(self, x, fc):
@@ -232,9 +268,10 @@ class DynamicPTQModel:
         """``mean`` / ``std``: the Normalize constants applied to raw uint8
         NHWC images.  ``granularity``: "batch" (quantize_dynamic's per-call
         activation range) or "sample" (one range per image).  ``body``:
-        "torch" (MIOpen convolutions) or "hip" (ops.conv3x3_f32); with
-        "sample" and "hip" an image's logits are bit-identical whatever batch
-        it arrives in (see DynamicQuantConvNet)."""
+        "torch" (MIOpen convolutions), "hip" (ops.conv3x3_f32) or "int8"
+        (ops.conv3x3_dyn, the convolutions dynamically quantized per image as
+        well); with "sample" and "hip" or "int8" an image's logits are
+        bit-identical whatever batch it arrives in (see DynamicQuantConvNet)."""
         check_granularity(granularity)
         check_body(body)
         self.fp32_model = self.fp32_model.cpu().eval()
@@ -245,5 +282,6 @@ class DynamicPTQModel:
 
     def get_model_size(self):
         buf = io.BytesIO()
-        torch.save([t for fc in self.quantized_model.fc for t in fc], buf)
+        q = self.quantized_model
+        torch.save([t for fc in q.fc for t in fc] + [t for c in q.qconvs or () for t in c[:4]], buf)
         return buf.tell() / (1024 * 1024)

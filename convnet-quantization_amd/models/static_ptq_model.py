@@ -51,13 +51,15 @@ class StaticPTQModel:
         ("batch" or "sample") belongs to mode="reference": whose range gives
         the dynamic fc1/fc2 their activation qparams (DynamicQuantConvNet);
         the static net has no dynamic layer, so "sample" is an error there.
-        ``body`` ("torch" or "hip") belongs to mode="reference" too: who runs
-        its fp32 convolutions; the static net has none, so "hip" is an error."""
+        ``body`` ("torch", "hip" or "int8") belongs to mode="reference" too:
+        who runs its six convolutions (fp32 through MIOpen, fp32 through the
+        deterministic HIP kernel, or dynamically quantized int8); the static
+        net has no such choice, so anything but "torch" is an error."""
         from models.dynamic_ptq_model import DynamicQuantConvNet, check_body, check_granularity
         check_granularity(granularity)
         check_body(body)
         if self.mode == "static" and body != "torch":
-            raise ValueError('body="hip" needs mode="reference": the static net has no fp32 conv')
+            raise ValueError(f'body="{body}" needs mode="reference": the static net has no fp32 conv')
         if self.mode == "static" and granularity != "batch":
             raise ValueError('granularity="sample" needs mode="reference": the static net has no '
                              "dynamic layer")

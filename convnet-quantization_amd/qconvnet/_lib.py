@@ -143,6 +143,12 @@ SIGNATURES = {
     "qcn_conv3x3_f32_packed_size": (i32, [i32, i32]),
     "qcn_pack_conv3x3_weight_f32": (i32, [vp, i32, i32, vp]),
     "qcn_conv3x3_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "qcn_conv3x3_dyn_packed_size": (i32, [i32, i32]),
+    "qcn_pack_conv3x3_weight_dyn": (i32, [vp, i32, i32, vp, vp]),
+    "qcn_conv3x3_dyn_stats_slots": (i32, [i32, i32, i32]),
+    "qcn_image_minmax_f32": (i32, [vp, i32, i64, vp, vp]),
+    "qcn_conv3x3_dyn": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp,
+                              i32, i32, i32, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -821,6 +821,80 @@ def conv3x3_f32(x, packed, cout, bias=None, affine=None, relu=False, pool=False,
     return out
 
 
+# --------------------------------------- dynamic int8 conv
+def pack_conv3x3_dyn(wq):
+    """Host packing of s8 OIHW [cout, cin, 3, 3] weights for ``conv3x3_dyn``:
+    (packed int8 numpy array in the kernel's operand order, wsum [cout] int32)."""
+    if torch.is_tensor(wq):
+        wq = wq.detach().cpu().numpy()
+    if wq.dtype != np.int8 or wq.ndim != 4 or wq.shape[2:] != (3, 3):
+        raise ValueError(f"pack_conv3x3_dyn: expected int8 [cout, cin, 3, 3], got {wq.dtype} {wq.shape}")
+    wq = np.ascontiguousarray(wq)
+    cout, cin = wq.shape[:2]
+    size = lib().qcn_conv3x3_dyn_packed_size(cin, cout)
+    if size < 0:
+        check(size, "conv3x3_dyn_packed_size")
+    out, wsum = np.empty(size, np.int8), np.empty(cout, np.int32)
+    check(lib().qcn_pack_conv3x3_weight_dyn(wq.ctypes.data, cout, cin, out.ctypes.data, wsum.ctypes.data),
+          "pack_conv3x3_dyn")
+    return out, wsum
+
+
+def image_minmax(x, out=None):
+    """Per-image (min, max) of a contiguous fp32 batch [n, ...] as a range
+    record [n, 1, 2] (one slot), the ``x_stats`` of the first ``conv3x3_dyn``."""
+    _need(x, torch.float32, "image_minmax.x")
+    n = x.shape[0]
+    if out is None:
+        out = torch.empty((n, 1, 2), dtype=torch.float32, device=x.device)
+    check(lib().qcn_image_minmax_f32(_ptr(x), n, x.numel() // n, _ptr(out), _stream()), "image_minmax")
+    return out
+
+
+def conv3x3_dyn(x, x_stats, packed, wsum, w_scale, cout, bias=None, affine=None, relu=False, pool=False,
+                x_nchw=False, y_nchw=False, reduce_range=False, want_stats=True, qparams=False, out=None):
+    """3x3 / stride 1 / padding 1 convolution on the int8 MFMA with every image
+    quantized by the qparams of its own range (``x_stats`` [n, slots, 2], from
+    ``image_minmax`` or the producing ``conv3x3_dyn``): fp32 in, fp32 out, the
+    same bits for an image in any batch.  ``packed``, ``wsum``: device tensors
+    of ``pack_conv3x3_dyn``; ``w_scale``: [1] or [cout]; epilogue and layouts
+    as ``conv3x3_f32``.  Returns (y, y_stats or None[, (scale [n] float32,
+    zero_point [n] int32)])."""
+    _need(x, torch.float32, "conv3x3_dyn.x")
+    _need(x_stats, torch.float32, "conv3x3_dyn.x_stats")
+    _need(packed, torch.int8, "conv3x3_dyn.packed")
+    _need(wsum, torch.int32, "conv3x3_dyn.wsum")
+    if x_nchw:
+        n, cin, h, w = x.shape
+    else:
+        n, h, w, cin = x.shape
+    if packed.numel() != lib().qcn_conv3x3_dyn_packed_size(cin, cout) or wsum.numel() != cout:
+        raise ValueError("conv3x3_dyn.packed / wsum: size does not match (cin, cout)")
+    if x_stats.dim() != 3 or x_stats.shape[0] != n or x_stats.shape[2] != 2:
+        raise ValueError("conv3x3_dyn.x_stats: expected [n, slots, 2]")
+    if w_scale.numel() not in (1, cout):
+        raise ValueError("conv3x3_dyn.w_scale: expected 1 or cout scales")
+    oh, ow = (h // 2, w // 2) if pool else (h, w)
+    if out is None:
+        out = torch.empty((n, cout, oh, ow) if y_nchw else (n, oh, ow, cout), dtype=torch.float32,
+                          device=x.device)
+    stats = qp = None
+    if want_stats:
+        stats = torch.empty((n, lib().qcn_conv3x3_dyn_stats_slots(h, w, cout), 2), dtype=torch.float32,
+                            device=x.device)
+    if qparams:
+        qp = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+    alpha, beta = affine if affine is not None else (None, None)
+    check(lib().qcn_conv3x3_dyn(_ptr(x), n, h, w, cin, int(bool(x_nchw)), _ptr(x_stats), x_stats.shape[1],
+                                int(bool(reduce_range)), _ptr(packed), _ptr(wsum), _ptr(w_scale),
+                                int(w_scale.numel() > 1), cout, _ptr(bias), _ptr(alpha), _ptr(beta),
+                                int(bool(relu)), int(bool(pool)), int(bool(y_nchw)), _ptr(out),
+                                _ptr(stats), _ptr(qp), _stream()), "conv3x3_dyn")
+    if not qparams:
+        return out, stats
+    return out, stats, (qp[:, 0].clone(), qp[:, 1].contiguous().view(torch.int32))
+
+
 # ------------------------------------------------ SURVEY §8(f)2: ResNet blocks
 def pack_conv_kmajor(w_oihw: np.ndarray):
     """s8 OIHW -> (chunk-major [kh*kw*cin/32, cout, 32] bytes, wsum int32)."""

@@ -703,6 +703,53 @@ int qcn_conv3x3_f32(const float* x, int nimg, int h, int w, int cin, int x_nchw,
                     const float* w_packed, int cout, const float* bias, const float* alpha,
                     const float* beta, int relu, int pool, int y_nchw, float* y, void* stream);
 
+/* ---- dynamically quantized int8 3x3 conv ----------------------
+ * 3x3, stride 1, padding 1, fp32 in / out, the products on
+ * v_mfma_i32_16x16x64_i8.  Per image n, nothing calibrated:
+ *   (s_x, z_x) = ChooseQuantizationParams(min x_n, max x_n, reduce_range)
+ *   q   = clamp(rne(min(fmaf(x, 1 / s_x, z_x), 255)), 0, 255)      (LEGACY quantize)
+ *   acc = sum over taps and ci of (q - z_x) * wq[c][ci][tap]       (int32, padding = 0)
+ *   t   = fmaf((float)acc, s_x * s_w[c], bias[c])                  (s_w[0] when !per_channel)
+ *   t   = fmaf(t, alpha[c], beta[c]); t = max(t, 0); max over the 2x2 window
+ * (the steps of the last line optional, as in qcn_conv3x3_f32).  Integer sums
+ * are exact, so an image's result is the same bits in any batch.  NaN and inf
+ * are outside the contract.
+ * cin <= 7310, the largest value with 9 * cin * 255 * 128 <= 2^31 - 1 (the
+ * worst-case |acc| of u8 codes against s8 weights); larger is
+ * QCN_ERR_UNSUPPORTED, before any launch.
+ * Range records ("stats"): float [nimg][slots][2] = (min, max) per slot; an
+ * image's range is the min / max over its slots.  A conv writes one slot per
+ * block of its grid; every slot of every image is written by every call. */
+/* Bytes of the packed weights (negative: a status). */
+int qcn_conv3x3_dyn_packed_size(int cin, int cout);
+/* Host packing of OIHW s8 weights into the MFMA B-operand lane order, and
+ * wsum[c] = sum of wq[c].  The K unit is 16 channels of one tap; cin runs in
+ * chunks of 256 channels (ncgc = 16-channel groups of the chunk, 16 but for
+ * the last), a full chunk is 36 steps of 4 units:
+ *   out[((ct * steps + step) * 64 + lane) * 16 + b] = w[16 ct + lane % 16][ci][tap]
+ * chunk = step / 36, u = 4 (step - 36 chunk) + lane / 16, tap = u / ncgc,
+ * ci = 256 chunk + 16 (u % ncgc) + b; 0 where tap > 8, ci >= cin or the column
+ * is past cout (4 * ceil(cout / 64) column tiles ct). */
+int qcn_pack_conv3x3_weight_dyn(const int8_t* w_oihw, int cout, int cin, int8_t* out, int32_t* wsum);
+/* Slots per image of the stats a conv of this geometry writes. */
+int qcn_conv3x3_dyn_stats_slots(int h, int w, int cout);
+/* min / max of each image's count contiguous floats (any layout) -> one slot:
+ * stats[n][0].  The range record of the first layer's input. */
+int qcn_image_minmax_f32(const float* x, int nimg, long long count, float* stats, void* stream);
+/* x, y: layouts as qcn_conv3x3_f32.  x_stats: the range record of x with
+ * x_slots slots per image.  y_stats (may be NULL): receives the range record
+ * of y, qcn_conv3x3_dyn_stats_slots(h, w, cout) slots per image.  x_qparams
+ * (may be NULL): receives [nimg][2] = (s_x as float, z_x as int32).  bias,
+ * alpha, beta may be NULL, alpha and beta only together.  w_packed 16-byte
+ * aligned.  QCN_ERR_ARG for bad pointers and sizes, QCN_ERR_UNSUPPORTED for
+ * cin > 7310 or more than 2^31 - 1 elements in x or y; both before any HIP
+ * call. */
+int qcn_conv3x3_dyn(const float* x, int nimg, int h, int w, int cin, int x_nchw, const float* x_stats,
+                    int x_slots, int reduce_range, const int8_t* w_packed, const int32_t* wsum,
+                    const float* w_scale, int per_channel, int cout, const float* bias,
+                    const float* alpha, const float* beta, int relu, int pool, int y_nchw, float* y,
+                    float* y_stats, float* x_qparams, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
