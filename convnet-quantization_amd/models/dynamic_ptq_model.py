@@ -52,6 +52,13 @@ def check_body(body):
     return body
 
 
+def check_pairs(pairs, body):
+    if pairs and body != "int8":
+        raise ValueError(f'pairs=True needs body="int8" (got body="{body}"): only the dynamic int8 '
+                         "convs have a pair kernel")
+    return bool(pairs)
+
+
 class DynamicQuantConvNet:
     """fp32 convs (+ optional BN fold) and dynamic-int8 fc1/fc2 on the GPU.
     Raw uint8 NHWC images are normalised with ``mean`` / ``std`` on the device
@@ -77,12 +84,19 @@ class DynamicQuantConvNet:
     quantizes each image's activations with the qparams of that image's own
     min/max (full 8 bits: ``reduce_range`` applies to the Linears only) and
     accumulates in int32, so the same invariance holds and the convolutions are
-    no longer the reference's fp32 ops."""
+    no longer the reference's fp32 ops.
+
+    ``pairs`` (body="int8" only, default False): a layer without a pool and
+    its successor run as one ops.conv3x3_dyn_pair launch wherever
+    ops.conv3x3_dyn_pair_supported serves the shape (conv3 + conv4 and
+    conv5 + conv6), the activation between them handed over as u8
+    in LDS.  The bits are those of ``pairs=False``."""
 
     def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
-                 std=CIFAR_STD, granularity="batch", body="torch", conv_per_channel=True):
+                 std=CIFAR_STD, granularity="batch", body="torch", conv_per_channel=True, pairs=False):
         self.granularity = check_granularity(granularity)
         self.body = check_body(body)
+        self.pairs = check_pairs(pairs, body)
         self.device = cuda_device(device)
         self.ntab = Q.normalize_table(mean, std).to(self.device)
         self.reduce_range = reduce_range
@@ -178,14 +192,29 @@ class DynamicQuantConvNet:
     def _features_int8(self, x):
         """One per-image min/max launch, then six dynamic int8 convs, each
         handing its output's per-image range to the next (layouts as
-        _features_hip)."""
+        _features_hip).  With ``pairs``, a layer without a pool and the next
+        one are one launch where the pair kernel serves the shape."""
         x = x.contiguous()
         stats = ops.image_minmax(x)
         last = len(self.qconvs) - 1
-        for i, (wp, wsum, s_w, b, affine) in enumerate(self.qconvs):
-            x, stats = ops.conv3x3_dyn(x, stats, wp, wsum, s_w, CONV_TABLE[i][1], bias=b, affine=affine,
-                                       relu=True, pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0,
-                                       y_nchw=i == last, want_stats=i != last)
+        h, w = x.shape[2:]
+        i = 0
+        while i <= last:
+            (wp, wsum, s_w, b, affine), (cin, cout, pool) = self.qconvs[i], CONV_TABLE[i]
+            if (self.pairs and i < last and not pool
+                    and ops.conv3x3_dyn_pair_supported(h, w, cin, cout, CONV_TABLE[i + 1][1])):
+                layers = [ops.DynLayer(q[0], q[1], q[2], CONV_TABLE[j][1], bias=q[3], affine=q[4], relu=True)
+                          for j, q in ((i, self.qconvs[i]), (i + 1, self.qconvs[i + 1]))]
+                i, pool = i + 1, CONV_TABLE[i + 1][2]
+                x, stats = ops.conv3x3_dyn_pair(x, stats, layers[0], layers[1], pool=bool(pool),
+                                                x_nchw=i == 1, y_nchw=i == last, want_stats=i != last)
+            else:
+                x, stats = ops.conv3x3_dyn(x, stats, wp, wsum, s_w, cout, bias=b, affine=affine, relu=True,
+                                           pool=bool(pool), x_nchw=i == 0, y_nchw=i == last,
+                                           want_stats=i != last)
+            if pool:
+                h, w = h // 2, w // 2
+            i += 1
         return x.reshape(x.shape[0], -1)
 
     def _linear(self, x, fc):
@@ -264,20 +293,22 @@ class DynamicPTQModel:
     def __call__(self, x):
         return self.forward(x)
 
-    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD, granularity="batch", body="torch"):
+    def quantize(self, mean=CIFAR_MEAN, std=CIFAR_STD, granularity="batch", body="torch", pairs=False):
         """``mean`` / ``std``: the Normalize constants applied to raw uint8
         NHWC images.  ``granularity``: "batch" (quantize_dynamic's per-call
         activation range) or "sample" (one range per image).  ``body``:
         "torch" (MIOpen convolutions), "hip" (ops.conv3x3_f32) or "int8"
         (ops.conv3x3_dyn, the convolutions dynamically quantized per image as
         well); with "sample" and "hip" or "int8" an image's logits are
-        bit-identical whatever batch it arrives in (see DynamicQuantConvNet)."""
+        bit-identical whatever batch it arrives in (see DynamicQuantConvNet).
+        ``pairs``: with "int8", conv3 + conv4 and conv5 + conv6 as one launch
+        each (ops.conv3x3_dyn_pair), the same bits."""
         check_granularity(granularity)
-        check_body(body)
+        check_pairs(pairs, check_body(body))
         self.fp32_model = self.fp32_model.cpu().eval()
         self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=True,
                                                    device=self.device, mean=mean, std=std,
-                                                   granularity=granularity, body=body)
+                                                   granularity=granularity, body=body, pairs=pairs)
         return self.quantized_model
 
     def get_model_size(self):

@@ -40,7 +40,7 @@ class StaticPTQModel:
 
     def quantize(self, calibration_data_loader=None, per_channel=False, calibration_device="cpu",
                  max_batches=None, observer="minmax", mean=data.CIFAR_MEAN, std=data.CIFAR_STD,
-                 granularity="batch", body="torch"):
+                 granularity="batch", body="torch", pairs=False):
         """Calibrate (fp32, BN folded — the reference quantizes on the CPU, so
         does the default here) and build the int8 GPU model.  observer:
         "minmax" (default) or "histogram", torch.ao's default
@@ -54,10 +54,11 @@ class StaticPTQModel:
         ``body`` ("torch", "hip" or "int8") belongs to mode="reference" too:
         who runs its six convolutions (fp32 through MIOpen, fp32 through the
         deterministic HIP kernel, or dynamically quantized int8); the static
-        net has no such choice, so anything but "torch" is an error."""
-        from models.dynamic_ptq_model import DynamicQuantConvNet, check_body, check_granularity
+        net has no such choice, so anything but "torch" is an error.
+        ``pairs`` goes with body="int8" (DynamicQuantConvNet)."""
+        from models.dynamic_ptq_model import DynamicQuantConvNet, check_body, check_granularity, check_pairs
         check_granularity(granularity)
-        check_body(body)
+        check_pairs(pairs, check_body(body))
         if self.mode == "static" and body != "torch":
             raise ValueError(f'body="{body}" needs mode="reference": the static net has no fp32 conv')
         if self.mode == "static" and granularity != "batch":
@@ -67,7 +68,7 @@ class StaticPTQModel:
         if self.mode == "reference":
             self.quantized_model = DynamicQuantConvNet(self.fp32_model.state_dict(), fold=False,
                                                        device=self.device, mean=mean, std=std,
-                                                       granularity=granularity, body=body)
+                                                       granularity=granularity, body=body, pairs=pairs)
             return self.quantized_model
         folded = fold_state_dict(self.fp32_model.state_dict())
         batches = data.calibration_batches(calibration_data_loader, max_batches)

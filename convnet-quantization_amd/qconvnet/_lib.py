@@ -48,6 +48,13 @@ class ResizeImg(C.Structure):
     _fields_ = [("offset", C.c_longlong)] + [(k, C.c_int32) for k in ("h", "w", "oh", "ow", "top", "left")]
 
 
+class DynLayer(C.Structure):
+    """qcn_dyn_layer_t"""
+    _fields_ = [("w_packed", C.c_void_p), ("wsum", C.c_void_p), ("w_scale", C.c_void_p),
+                ("per_channel", C.c_int32), ("channels", C.c_int32), ("bias", C.c_void_p),
+                ("alpha", C.c_void_p), ("beta", C.c_void_p), ("relu", C.c_int32)]
+
+
 vp = C.c_void_p
 i32 = C.c_int
 i64 = C.c_longlong
@@ -149,6 +156,9 @@ SIGNATURES = {
     "qcn_image_minmax_f32": (i32, [vp, i32, i64, vp, vp]),
     "qcn_conv3x3_dyn": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp,
                               i32, i32, i32, vp, vp, vp, vp]),
+    "qcn_conv3x3_dyn_pair_supported": (i32, [i32, i32, i32, i32, i32]),
+    "qcn_conv3x3_dyn_pair": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, C.POINTER(DynLayer),
+                                   C.POINTER(DynLayer), i32, i32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ copies its counts to the host, one sync per call.
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -893,6 +894,76 @@ def conv3x3_dyn(x, x_stats, packed, wsum, w_scale, cout, bias=None, affine=None,
     if not qparams:
         return out, stats
     return out, stats, (qp[:, 0].clone(), qp[:, 1].contiguous().view(torch.int32))
+
+
+# ------------------------------- dynamic int8 conv pairs
+class DynLayer(NamedTuple):
+    """One layer of ``conv3x3_dyn_pair``: the weight, scale and epilogue
+    arguments of ``conv3x3_dyn``."""
+    packed: torch.Tensor
+    wsum: torch.Tensor
+    w_scale: torch.Tensor
+    channels: int
+    bias: Optional[torch.Tensor] = None
+    affine: Optional[tuple] = None
+    relu: bool = False
+
+
+def conv3x3_dyn_pair_supported(h, w, cin, cmid, cout):
+    """Whether ``conv3x3_dyn_pair`` serves the shape (a function of the shape alone)."""
+    return bool(lib().qcn_conv3x3_dyn_pair_supported(h, w, cin, cmid, cout))
+
+
+def _dyn_layer(layer, cin, name):
+    _need(layer.packed, torch.int8, name + ".packed")
+    _need(layer.wsum, torch.int32, name + ".wsum")
+    ch = layer.channels
+    if layer.packed.numel() != lib().qcn_conv3x3_dyn_packed_size(cin, ch) or layer.wsum.numel() != ch:
+        raise ValueError(f"{name}.packed / wsum: size does not match (cin, channels)")
+    if layer.w_scale.numel() not in (1, ch):
+        raise ValueError(f"{name}.w_scale: expected 1 or channels scales")
+    alpha, beta = layer.affine if layer.affine is not None else (None, None)
+    return _lib.DynLayer(_ptr(layer.packed), _ptr(layer.wsum), _ptr(layer.w_scale),
+                         int(layer.w_scale.numel() > 1), ch, _ptr(layer.bias), _ptr(alpha), _ptr(beta),
+                         int(bool(layer.relu)))
+
+
+def conv3x3_dyn_pair(x, x_stats, layer_a, layer_b, pool=False, x_nchw=False, y_nchw=False,
+                     reduce_range=False, want_stats=True, qparams=False, out=None):
+    """``conv3x3_dyn`` with ``layer_a`` (no pool) then ``conv3x3_dyn`` with
+    ``layer_b`` (``pool``, ``y_nchw``) in one launch, the activation between
+    them handed over as u8 codes in LDS: the same bits as the two calls, for
+    the shapes of ``conv3x3_dyn_pair_supported`` (others raise).  The layers are
+    ``DynLayer`` tuples.  Returns (y, y_stats [n, 1, 2] or None[, qparams of x,
+    qparams of the intermediate activation]), each qparams a (scale [n]
+    float32, zero_point [n] int32)."""
+    _need(x, torch.float32, "conv3x3_dyn_pair.x")
+    _need(x_stats, torch.float32, "conv3x3_dyn_pair.x_stats")
+    if x_nchw:
+        n, cin, h, w = x.shape
+    else:
+        n, h, w, cin = x.shape
+    if x_stats.dim() != 3 or x_stats.shape[0] != n or x_stats.shape[2] != 2:
+        raise ValueError("conv3x3_dyn_pair.x_stats: expected [n, slots, 2]")
+    cmid, cout = layer_a.channels, layer_b.channels
+    la = _dyn_layer(layer_a, cin, "conv3x3_dyn_pair.layer_a")
+    lb = _dyn_layer(layer_b, cmid, "conv3x3_dyn_pair.layer_b")
+    oh, ow = (h // 2, w // 2) if pool else (h, w)
+    if out is None:
+        out = torch.empty((n, cout, oh, ow) if y_nchw else (n, oh, ow, cout), dtype=torch.float32,
+                          device=x.device)
+    stats = qx = qm = None
+    if want_stats:
+        stats = torch.empty((n, 1, 2), dtype=torch.float32, device=x.device)
+    if qparams:
+        qx, qm = (torch.empty((n, 2), dtype=torch.float32, device=x.device) for _ in range(2))
+    check(lib().qcn_conv3x3_dyn_pair(_ptr(x), n, h, w, cin, int(bool(x_nchw)), _ptr(x_stats), x_stats.shape[1],
+                                     int(bool(reduce_range)), C.byref(la), C.byref(lb), int(bool(pool)),
+                                     int(bool(y_nchw)), _ptr(out), _ptr(stats), _ptr(qx), _ptr(qm), _stream()),
+          "conv3x3_dyn_pair")
+    if not qparams:
+        return out, stats
+    return (out, stats) + tuple((q[:, 0].clone(), q[:, 1].contiguous().view(torch.int32)) for q in (qx, qm))
 
 
 # ------------------------------------------------ SURVEY §8(f)2: ResNet blocks

@@ -750,6 +750,47 @@ int qcn_conv3x3_dyn(const float* x, int nimg, int h, int w, int cin, int x_nchw,
                     const float* alpha, const float* beta, int relu, int pool, int y_nchw, float* y,
                     float* y_stats, float* x_qparams, void* stream);
 
+/* ---- two dynamic int8 3x3 convs in one launch -----------------
+ * Layer A (no pool) then layer B, the intermediate activation handed over as
+ * u8 codes in LDS: one workgroup per image holds A's whole output in registers,
+ * reduces its range, quantizes it with that range's qparams and runs B.
+ * Contract: for every image, y, y_stats, x_qparams and mid_qparams are bit for
+ * bit those of
+ *   qcn_conv3x3_dyn(x, ..., layer A, pool = 0, y_nchw = 0, t, t_stats, x_qparams)
+ *   qcn_conv3x3_dyn(t, ..., t_stats, layer B, pool, y_nchw, y, y_stats, mid_qparams)
+ * with the same reduce_range in both (the range of y is one slot here, the
+ * min / max over the slots there).  Integer sums are exact and the fp32 steps
+ * are the same operations on the same values; min / max of the intermediate
+ * are order-independent but for the sign of a zero, which
+ * ChooseQuantizationParams does not distinguish.
+ * Served: h, w <= 8 with cmid, cout <= 256 (256 threads per image), else
+ * h, w <= 16 with cmid, cout <= 128 (512 threads per image); cin <= 7310. */
+typedef struct qcn_dyn_layer {
+  const int8_t* w_packed;   /* qcn_pack_conv3x3_weight_dyn, 16-byte aligned */
+  const int32_t* wsum;
+  const float* w_scale;     /* [channels] with per_channel, else [1] */
+  int per_channel;
+  int channels;             /* output channels of the layer */
+  const float* bias;        /* may be NULL */
+  const float* alpha;       /* may be NULL, only together with beta */
+  const float* beta;
+  int relu;
+} qcn_dyn_layer_t;
+/* 1 when qcn_conv3x3_dyn_pair serves the shape, else 0: a function of the
+ * shape alone (of (h, w, cmid, cout), and cin <= 7310). */
+int qcn_conv3x3_dyn_pair_supported(int h, int w, int cin, int cmid, int cout);
+/* x, x_stats, x_slots, reduce_range, x_qparams: as qcn_conv3x3_dyn.  la, lb:
+ * the two layers (cmid = la->channels, cout = lb->channels).  pool, y_nchw, y:
+ * layer B's.  y_stats (may be NULL): [nimg][1][2].  mid_qparams (may be NULL):
+ * [nimg][2] = (s, z as int32) of the intermediate activation.  QCN_ERR_ARG for
+ * bad pointers, sizes and alignment and for pool with odd h or w,
+ * QCN_ERR_UNSUPPORTED where qcn_conv3x3_dyn_pair_supported is 0 or x or y has
+ * more than 2^31 - 1 elements; both before any HIP call. */
+int qcn_conv3x3_dyn_pair(const float* x, int nimg, int h, int w, int cin, int x_nchw, const float* x_stats,
+                         int x_slots, int reduce_range, const qcn_dyn_layer_t* la, const qcn_dyn_layer_t* lb,
+                         int pool, int y_nchw, float* y, float* y_stats, float* x_qparams, float* mid_qparams,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
