@@ -53,10 +53,12 @@ def check_body(body):
 
 
 def check_pairs(pairs, body):
+    if not (isinstance(pairs, bool) or pairs == "all"):
+        raise ValueError(f'unknown pairs {pairs!r} (expected False, True or "all")')
     if pairs and body != "int8":
-        raise ValueError(f'pairs=True needs body="int8" (got body="{body}"): only the dynamic int8 '
+        raise ValueError(f'pairs={pairs!r} needs body="int8" (got body="{body}"): only the dynamic int8 '
                          "convs have a pair kernel")
-    return bool(pairs)
+    return pairs
 
 
 class DynamicQuantConvNet:
@@ -90,7 +92,10 @@ class DynamicQuantConvNet:
     its successor run as one ops.conv3x3_dyn_pair launch wherever
     ops.conv3x3_dyn_pair_supported serves the shape (conv3 + conv4 and
     conv5 + conv6), the activation between them handed over as u8
-    in LDS.  The bits are those of ``pairs=False``."""
+    in LDS.  ``pairs="all"`` also takes ops.conv3x3_dyn_pair32 where the first
+    kernel does not serve the shape and that one does (conv1 + conv2; DESIGN
+    §26): features() is then min/max and three pair launches.  The bits are
+    those of ``pairs=False``."""
 
     def __init__(self, state_dict, fold=True, device="cuda", reduce_range=True, mean=CIFAR_MEAN,
                  std=CIFAR_STD, granularity="batch", body="torch", conv_per_channel=True, pairs=False):
@@ -193,7 +198,8 @@ class DynamicQuantConvNet:
         """One per-image min/max launch, then six dynamic int8 convs, each
         handing its output's per-image range to the next (layouts as
         _features_hip).  With ``pairs``, a layer without a pool and the next
-        one are one launch where the pair kernel serves the shape."""
+        one are one launch where a pair kernel serves the shape (the 32 x 32
+        one with ``pairs="all"`` only)."""
         x = x.contiguous()
         stats = ops.image_minmax(x)
         last = len(self.qconvs) - 1
@@ -201,13 +207,19 @@ class DynamicQuantConvNet:
         i = 0
         while i <= last:
             (wp, wsum, s_w, b, affine), (cin, cout, pool) = self.qconvs[i], CONV_TABLE[i]
-            if (self.pairs and i < last and not pool
-                    and ops.conv3x3_dyn_pair_supported(h, w, cin, cout, CONV_TABLE[i + 1][1])):
+            pair = None
+            if self.pairs and i < last and not pool:
+                shape = (h, w, cin, cout, CONV_TABLE[i + 1][1])
+                if ops.conv3x3_dyn_pair_supported(*shape):
+                    pair = ops.conv3x3_dyn_pair
+                elif self.pairs == "all" and ops.conv3x3_dyn_pair32_supported(*shape):
+                    pair = ops.conv3x3_dyn_pair32
+            if pair is not None:
                 layers = [ops.DynLayer(q[0], q[1], q[2], CONV_TABLE[j][1], bias=q[3], affine=q[4], relu=True)
                           for j, q in ((i, self.qconvs[i]), (i + 1, self.qconvs[i + 1]))]
                 i, pool = i + 1, CONV_TABLE[i + 1][2]
-                x, stats = ops.conv3x3_dyn_pair(x, stats, layers[0], layers[1], pool=bool(pool),
-                                                x_nchw=i == 1, y_nchw=i == last, want_stats=i != last)
+                x, stats = pair(x, stats, layers[0], layers[1], pool=bool(pool),
+                                x_nchw=i == 1, y_nchw=i == last, want_stats=i != last)
             else:
                 x, stats = ops.conv3x3_dyn(x, stats, wp, wsum, s_w, cout, bias=b, affine=affine, relu=True,
                                            pool=bool(pool), x_nchw=i == 0, y_nchw=i == last,
@@ -302,7 +314,8 @@ class DynamicPTQModel:
         well); with "sample" and "hip" or "int8" an image's logits are
         bit-identical whatever batch it arrives in (see DynamicQuantConvNet).
         ``pairs``: with "int8", conv3 + conv4 and conv5 + conv6 as one launch
-        each (ops.conv3x3_dyn_pair), the same bits."""
+        each (ops.conv3x3_dyn_pair), with "all" conv1 + conv2 too
+        (ops.conv3x3_dyn_pair32), the same bits."""
         check_granularity(granularity)
         check_pairs(pairs, check_body(body))
         self.fp32_model = self.fp32_model.cpu().eval()

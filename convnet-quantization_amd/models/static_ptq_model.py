@@ -55,7 +55,8 @@ class StaticPTQModel:
         who runs its six convolutions (fp32 through MIOpen, fp32 through the
         deterministic HIP kernel, or dynamically quantized int8); the static
         net has no such choice, so anything but "torch" is an error.
-        ``pairs`` goes with body="int8" (DynamicQuantConvNet)."""
+        ``pairs`` (False, True or "all") goes with body="int8"
+        (DynamicQuantConvNet)."""
         from models.dynamic_ptq_model import DynamicQuantConvNet, check_body, check_granularity, check_pairs
         check_granularity(granularity)
         check_pairs(pairs, check_body(body))

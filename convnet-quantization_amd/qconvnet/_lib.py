@@ -159,6 +159,9 @@ SIGNATURES = {
     "qcn_conv3x3_dyn_pair_supported": (i32, [i32, i32, i32, i32, i32]),
     "qcn_conv3x3_dyn_pair": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, C.POINTER(DynLayer),
                                    C.POINTER(DynLayer), i32, i32, vp, vp, vp, vp, vp]),
+    "qcn_conv3x3_dyn_pair32_supported": (i32, [i32, i32, i32, i32, i32]),
+    "qcn_conv3x3_dyn_pair32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, C.POINTER(DynLayer),
+                                     C.POINTER(DynLayer), i32, i32, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -928,26 +928,20 @@ def _dyn_layer(layer, cin, name):
                          int(bool(layer.relu)))
 
 
-def conv3x3_dyn_pair(x, x_stats, layer_a, layer_b, pool=False, x_nchw=False, y_nchw=False,
-                     reduce_range=False, want_stats=True, qparams=False, out=None):
-    """``conv3x3_dyn`` with ``layer_a`` (no pool) then ``conv3x3_dyn`` with
-    ``layer_b`` (``pool``, ``y_nchw``) in one launch, the activation between
-    them handed over as u8 codes in LDS: the same bits as the two calls, for
-    the shapes of ``conv3x3_dyn_pair_supported`` (others raise).  The layers are
-    ``DynLayer`` tuples.  Returns (y, y_stats [n, 1, 2] or None[, qparams of x,
-    qparams of the intermediate activation]), each qparams a (scale [n]
-    float32, zero_point [n] int32)."""
-    _need(x, torch.float32, "conv3x3_dyn_pair.x")
-    _need(x_stats, torch.float32, "conv3x3_dyn_pair.x_stats")
+def _conv3x3_dyn_pair(name, x, x_stats, layer_a, layer_b, pool, x_nchw, y_nchw, reduce_range, want_stats,
+                      qparams, out):
+    """The pair entry ``qcn_<name>`` (one argument list for both pair kernels)."""
+    _need(x, torch.float32, name + ".x")
+    _need(x_stats, torch.float32, name + ".x_stats")
     if x_nchw:
         n, cin, h, w = x.shape
     else:
         n, h, w, cin = x.shape
     if x_stats.dim() != 3 or x_stats.shape[0] != n or x_stats.shape[2] != 2:
-        raise ValueError("conv3x3_dyn_pair.x_stats: expected [n, slots, 2]")
+        raise ValueError(name + ".x_stats: expected [n, slots, 2]")
     cmid, cout = layer_a.channels, layer_b.channels
-    la = _dyn_layer(layer_a, cin, "conv3x3_dyn_pair.layer_a")
-    lb = _dyn_layer(layer_b, cmid, "conv3x3_dyn_pair.layer_b")
+    la = _dyn_layer(layer_a, cin, name + ".layer_a")
+    lb = _dyn_layer(layer_b, cmid, name + ".layer_b")
     oh, ow = (h // 2, w // 2) if pool else (h, w)
     if out is None:
         out = torch.empty((n, cout, oh, ow) if y_nchw else (n, oh, ow, cout), dtype=torch.float32,
@@ -957,13 +951,44 @@ def conv3x3_dyn_pair(x, x_stats, layer_a, layer_b, pool=False, x_nchw=False, y_n
         stats = torch.empty((n, 1, 2), dtype=torch.float32, device=x.device)
     if qparams:
         qx, qm = (torch.empty((n, 2), dtype=torch.float32, device=x.device) for _ in range(2))
-    check(lib().qcn_conv3x3_dyn_pair(_ptr(x), n, h, w, cin, int(bool(x_nchw)), _ptr(x_stats), x_stats.shape[1],
-                                     int(bool(reduce_range)), C.byref(la), C.byref(lb), int(bool(pool)),
-                                     int(bool(y_nchw)), _ptr(out), _ptr(stats), _ptr(qx), _ptr(qm), _stream()),
-          "conv3x3_dyn_pair")
+    check(getattr(lib(), "qcn_" + name)(_ptr(x), n, h, w, cin, int(bool(x_nchw)), _ptr(x_stats), x_stats.shape[1],
+                                        int(bool(reduce_range)), C.byref(la), C.byref(lb), int(bool(pool)),
+                                        int(bool(y_nchw)), _ptr(out), _ptr(stats), _ptr(qx), _ptr(qm), _stream()),
+          name)
     if not qparams:
         return out, stats
     return (out, stats) + tuple((q[:, 0].clone(), q[:, 1].contiguous().view(torch.int32)) for q in (qx, qm))
+
+
+def conv3x3_dyn_pair(x, x_stats, layer_a, layer_b, pool=False, x_nchw=False, y_nchw=False,
+                     reduce_range=False, want_stats=True, qparams=False, out=None):
+    """``conv3x3_dyn`` with ``layer_a`` (no pool) then ``conv3x3_dyn`` with
+    ``layer_b`` (``pool``, ``y_nchw``) in one launch, the activation between
+    them handed over as u8 codes in LDS: the same bits as the two calls, for
+    the shapes of ``conv3x3_dyn_pair_supported`` (others raise).  The layers are
+    ``DynLayer`` tuples.  Returns (y, y_stats [n, 1, 2] or None[, qparams of x,
+    qparams of the intermediate activation]), each qparams a (scale [n]
+    float32, zero_point [n] int32)."""
+    return _conv3x3_dyn_pair("conv3x3_dyn_pair", x, x_stats, layer_a, layer_b, pool, x_nchw, y_nchw, reduce_range,
+                             want_stats, qparams, out)
+
+
+# ------------------- dynamic int8 conv pair for 32 x 32 maps (DESIGN §26)
+def conv3x3_dyn_pair32_supported(h, w, cin, cmid, cout):
+    """Whether ``conv3x3_dyn_pair32`` serves the shape (a function of the shape alone)."""
+    return bool(lib().qcn_conv3x3_dyn_pair32_supported(h, w, cin, cmid, cout))
+
+
+def conv3x3_dyn_pair32(x, x_stats, layer_a, layer_b, pool=False, x_nchw=False, y_nchw=False,
+                       reduce_range=False, want_stats=True, qparams=False, out=None):
+    """``conv3x3_dyn_pair`` for maps up to 32 x 32 with up to 64 channels in,
+    between and out (conv1 + conv2): every wave of the image's workgroup keeps
+    two 8 x 8 x 64 pieces of ``layer_a``'s output in registers until the range
+    is known.  Same arguments, same return values, the same bits as the two
+    ``conv3x3_dyn`` calls; shapes outside ``conv3x3_dyn_pair32_supported``
+    raise."""
+    return _conv3x3_dyn_pair("conv3x3_dyn_pair32", x, x_stats, layer_a, layer_b, pool, x_nchw, y_nchw, reduce_range,
+                             want_stats, qparams, out)
 
 
 # ------------------------------------------------ SURVEY §8(f)2: ResNet blocks

@@ -791,6 +791,26 @@ int qcn_conv3x3_dyn_pair(const float* x, int nimg, int h, int w, int cin, int x_
                          int pool, int y_nchw, float* y, float* y_stats, float* x_qparams, float* mid_qparams,
                          void* stream);
 
+/* ---- the dynamic int8 conv pair for maps up to 32 x 32 --------
+ * qcn_conv3x3_dyn_pair's contract, argument list and argument checks for the
+ * shapes it refuses because a workgroup's registers cannot hold an image of the
+ * intermediate activation: h, w <= 32 with cin, cmid, cout <= 64 (conv1 +
+ * conv2).  One workgroup of 512 threads per image; every wave runs layer A for
+ * two 8 x 8 x 64 pieces of the map one after the other and keeps both results
+ * in registers until the image's range is known, then quantizes them, u8, into
+ * layer B's band in LDS.  y, y_stats, x_qparams and mid_qparams are bit for
+ * bit those of the two qcn_conv3x3_dyn calls. */
+/* 1 when qcn_conv3x3_dyn_pair32 serves the shape, else 0: a function of the
+ * shape alone. */
+int qcn_conv3x3_dyn_pair32_supported(int h, int w, int cin, int cmid, int cout);
+/* Arguments and statuses as qcn_conv3x3_dyn_pair, with
+ * qcn_conv3x3_dyn_pair32_supported as the predicate; every check comes before
+ * any HIP call. */
+int qcn_conv3x3_dyn_pair32(const float* x, int nimg, int h, int w, int cin, int x_nchw, const float* x_stats,
+                           int x_slots, int reduce_range, const qcn_dyn_layer_t* la, const qcn_dyn_layer_t* lb,
+                           int pool, int y_nchw, float* y, float* y_stats, float* x_qparams, float* mid_qparams,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

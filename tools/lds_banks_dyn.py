@@ -35,7 +35,8 @@ def worst(ncg, lcols):
 
 def handoff_ways(ncg, lcols):
     """Worst N-way conflict of the pair kernel's hand-off ds_write_b32 into the
-    mid band (csrc/conv_dyn_pair.hip), in the write model of
+    mid band (csrc/conv_dyn_pair.hip; width 32: csrc/conv_dyn_pair32.hip,
+    DESIGN §26, whose x band and mid band are both this layout), in the write model of
     lds_banks.conv1_write_ways (2 groups of 32 lanes, bank (a / 4) mod 32): lane
     (c16, g) writes channels 4 (c16 / 4) .. + 3 of position c16 % 4 of window g."""
     ps, rs, worst_ways = pixel_stride(ncg), row_stride(ncg, lcols), 0
@@ -53,5 +54,5 @@ if __name__ == "__main__":
     for ncg in range(1, 17):
         print(f"ncg {ncg:2d} (cin chunk {16 * ncg:3d}): PS {pixel_stride(ncg):3d} B, worst cycles at block widths "
               f"8 / 16 / 32: {' / '.join(str(worst(ncg, 8 * wpx + 2)) for wpx in (1, 2, 4))}; "
-              f"pair hand-off writes at widths 8 / 16: "
-              f"{' / '.join(str(handoff_ways(ncg, 8 * pgx + 2)) for pgx in (1, 2))}-way")
+              f"pair hand-off writes at widths 8 / 16 / 32: "
+              f"{' / '.join(str(handoff_ways(ncg, 8 * pgx + 2)) for pgx in (1, 2, 4))}-way")
