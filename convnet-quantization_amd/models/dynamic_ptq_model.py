@@ -17,7 +17,11 @@ with ``granularity="sample"`` the logits, independent of the batch.
 ``body="int8"`` goes past the reference: the six convolutions are
 dynamically quantized too, every image by its own range, on the int8 MFMA
 (csrc/conv_dyn.hip); nothing is calibrated and the batch independence holds
-by integer arithmetic.  The ResNet-50
+by integer arithmetic.  ``body="bf16"`` keeps the
+reference's operation at reduced operand precision: activations and weights are
+rounded to bf16, the sums are fp32 in a fixed order on the bf16 MFMA
+(csrc/conv_bf16.hip), and the layers hand their activations on as bf16.  The
+ResNet-50
 ``CustomDynamicQuantization`` of :13-216 needs torchvision and a weight
 download and is out of scope.
 """
@@ -37,7 +41,7 @@ from qconvnet.qmodel import cuda_device, fold_state_dict, normalized_input
 
 F32 = np.float32
 GRANULARITIES = ("batch", "sample")
-BODIES = ("torch", "hip", "int8")
+BODIES = ("torch", "hip", "int8", "bf16")
 
 
 def check_granularity(granularity):
@@ -87,6 +91,11 @@ class DynamicQuantConvNet:
     min/max (full 8 bits: ``reduce_range`` applies to the Linears only) and
     accumulates in int32, so the same invariance holds and the convolutions are
     no longer the reference's fp32 ops.
+    "bf16" is ops.conv3x3_bf16: six launches like "hip", the operands rounded
+    to bf16 (8 bits of relative precision, fp32's range, nothing calibrated),
+    the sums and the epilogues in fp32 in an order fixed by the kernel, conv1
+    to conv5 writing bf16 NHWC, the bits the next layer would round to anyway:
+    the same invariance at half the activation bytes.
 
     ``pairs`` (body="int8" only, default False): a layer without a pool and
     its successor run as one ops.conv3x3_dyn_pair launch wherever
@@ -128,6 +137,12 @@ class DynamicQuantConvNet:
         if self.body == "hip":
             # (packed weights, bias, BN as fma(x, alpha, beta) or None) per conv
             self.packed = [(self._t(ops.pack_conv3x3_f32(w)), self._t(b),
+                            tuple(self._t(a) for a in Q.bn_eval_affine(*bn)) if bn else None)
+                           for w, b, bn in convs]
+        self.bconvs = None
+        if self.body == "bf16":
+            # (packed bf16 weights, bias, BN as fma(x, alpha, beta) or None) per conv
+            self.bconvs = [(self._t(ops.pack_conv3x3_bf16(w)), self._t(b),
                             tuple(self._t(a) for a in Q.bn_eval_affine(*bn)) if bn else None)
                            for w, b, bn in convs]
         self.qconvs = None
@@ -176,6 +191,8 @@ class DynamicQuantConvNet:
             return self._features_hip(x)
         if self.body == "int8":
             return self._features_int8(x)
+        if self.body == "bf16":
+            return self._features_bf16(x)
         for i, (w, b, bn) in enumerate(self.convs):
             x = F.conv2d(x, w, b, padding=1)
             if bn is not None:
@@ -192,6 +209,17 @@ class DynamicQuantConvNet:
         for i, (wp, b, affine) in enumerate(self.packed):
             x = ops.conv3x3_f32(x, wp, CONV_TABLE[i][1], bias=b, affine=affine, relu=True,
                                 pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0, y_nchw=i == last)
+        return x.reshape(x.shape[0], -1)
+
+    def _features_bf16(self, x):
+        """fp32 NCHW in at conv1, bf16 NHWC between the layers, fp32
+        NCHW-flatten out of conv6."""
+        x = x.contiguous()
+        last = len(self.bconvs) - 1
+        for i, (wp, b, affine) in enumerate(self.bconvs):
+            x = ops.conv3x3_bf16(x, wp, CONV_TABLE[i][1], bias=b, affine=affine, relu=True,
+                                 pool=bool(CONV_TABLE[i][2]), x_nchw=i == 0, y_nchw=i == last,
+                                 y_bf16=i != last)
         return x.reshape(x.shape[0], -1)
 
     def _features_int8(self, x):
@@ -309,9 +337,10 @@ class DynamicPTQModel:
         """``mean`` / ``std``: the Normalize constants applied to raw uint8
         NHWC images.  ``granularity``: "batch" (quantize_dynamic's per-call
         activation range) or "sample" (one range per image).  ``body``:
-        "torch" (MIOpen convolutions), "hip" (ops.conv3x3_f32) or "int8"
+        "torch" (MIOpen convolutions), "hip" (ops.conv3x3_f32), "int8"
         (ops.conv3x3_dyn, the convolutions dynamically quantized per image as
-        well); with "sample" and "hip" or "int8" an image's logits are
+        well) or "bf16" (ops.conv3x3_bf16, bf16 operands and hand-offs, fp32
+        sums); with "sample" and "hip", "int8" or "bf16" an image's logits are
         bit-identical whatever batch it arrives in (see DynamicQuantConvNet).
         ``pairs``: with "int8", conv3 + conv4 and conv5 + conv6 as one launch
         each (ops.conv3x3_dyn_pair), with "all" conv1 + conv2 too
@@ -327,5 +356,6 @@ class DynamicPTQModel:
     def get_model_size(self):
         buf = io.BytesIO()
         q = self.quantized_model
-        torch.save([t for fc in q.fc for t in fc] + [t for c in q.qconvs or () for t in c[:4]], buf)
+        torch.save([t for fc in q.fc for t in fc] + [t for c in q.qconvs or () for t in c[:4]] +
+                   [c[0] for c in q.bconvs or ()], buf)
         return buf.tell() / (1024 * 1024)

@@ -51,9 +51,10 @@ class StaticPTQModel:
         ("batch" or "sample") belongs to mode="reference": whose range gives
         the dynamic fc1/fc2 their activation qparams (DynamicQuantConvNet);
         the static net has no dynamic layer, so "sample" is an error there.
-        ``body`` ("torch", "hip" or "int8") belongs to mode="reference" too:
-        who runs its six convolutions (fp32 through MIOpen, fp32 through the
-        deterministic HIP kernel, or dynamically quantized int8); the static
+        ``body`` ("torch", "hip", "int8" or "bf16") belongs to mode="reference"
+        too: who runs its six convolutions (fp32 through MIOpen, fp32 through
+        the deterministic HIP kernel, dynamically quantized int8, or bf16
+        operands with fp32 sums); the static
         net has no such choice, so anything but "torch" is an error.
         ``pairs`` (False, True or "all") goes with body="int8"
         (DynamicQuantConvNet)."""

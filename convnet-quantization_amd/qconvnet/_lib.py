@@ -16,6 +16,7 @@ QCN_OK = 0
 QCN_ERR_ARG = -1
 QCN_ERR_UNSUPPORTED = -2
 QCN_ERR_HIP = -3
+QCN_FMT_F32_NHWC, QCN_FMT_F32_NCHW, QCN_FMT_BF16_NHWC = 0, 1, 2   # qcn_conv3x3_bf16 tensor formats
 _ERRS = {QCN_ERR_ARG: "invalid argument", QCN_ERR_UNSUPPORTED: "unsupported shape",
          QCN_ERR_HIP: "HIP runtime error"}
 
@@ -162,6 +163,9 @@ SIGNATURES = {
     "qcn_conv3x3_dyn_pair32_supported": (i32, [i32, i32, i32, i32, i32]),
     "qcn_conv3x3_dyn_pair32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, C.POINTER(DynLayer),
                                      C.POINTER(DynLayer), i32, i32, vp, vp, vp, vp, vp]),
+    "qcn_conv3x3_bf16_packed_size": (i32, [i32, i32]),
+    "qcn_pack_conv3x3_weight_bf16": (i32, [vp, i32, i32, vp]),
+    "qcn_conv3x3_bf16": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp]),
 }
 
 _lib = None

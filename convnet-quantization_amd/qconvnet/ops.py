@@ -896,6 +896,66 @@ def conv3x3_dyn(x, x_stats, packed, wsum, w_scale, cout, bias=None, affine=None,
     return out, stats, (qp[:, 0].clone(), qp[:, 1].contiguous().view(torch.int32))
 
 
+# ------------------------------------------- bf16 conv
+def pack_conv3x3_bf16(w):
+    """Host packing of fp32 OIHW [cout, cin, 3, 3] weights (numpy array or
+    tensor) for ``conv3x3_bf16``: rounded to bf16 (nearest even) in the kernel's
+    operand order (include/qconvnet.h), an int16 numpy array of bf16 bits."""
+    if torch.is_tensor(w):
+        w = w.detach().cpu().numpy()
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise ValueError(f"pack_conv3x3_bf16: expected [cout, cin, 3, 3], got {w.shape}")
+    cout, cin = w.shape[:2]
+    size = lib().qcn_conv3x3_bf16_packed_size(cin, cout)
+    if size < 0:
+        check(size, "conv3x3_bf16_packed_size")
+    out = np.empty(size // 2, np.int16)
+    check(lib().qcn_pack_conv3x3_weight_bf16(w.ctypes.data, cout, cin, out.ctypes.data),
+          "pack_conv3x3_bf16")
+    return out
+
+
+def conv3x3_bf16(x, packed, cout, bias=None, affine=None, relu=False, pool=False, x_nchw=False,
+                 y_nchw=False, y_bf16=False, out=None):
+    """3x3 / stride 1 / padding 1 convolution on the bf16 MFMA: operands rounded
+    to bf16 (nearest even), fp32 accumulation in an order fixed by the kernel,
+    so image i of the result does not depend on the rest of the batch.  ``x``:
+    float32 NHWC [n, h, w, cin] (NCHW with ``x_nchw``) or bfloat16 NHWC;
+    ``packed``: device tensor of ``pack_conv3x3_bf16``; epilogue as
+    ``conv3x3_f32``, in fp32.  Returns float32 NHWC (NCHW with ``y_nchw``), or
+    with ``y_bf16`` the same values rounded to bfloat16, NHWC only.  Launches on
+    the current stream and does not synchronise."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"conv3x3_bf16.x: expected torch.float32 or torch.bfloat16, got {x.dtype}")
+    _need(x, x.dtype, "conv3x3_bf16.x")
+    _need(packed, torch.int16, "conv3x3_bf16.packed")
+    if x.dtype == torch.bfloat16 and x_nchw:
+        raise ValueError("conv3x3_bf16: a bfloat16 x is NHWC (x_nchw needs float32)")
+    if y_bf16 and y_nchw:
+        raise ValueError("conv3x3_bf16: y_bf16 is NHWC (y_nchw needs a float32 result)")
+    if x_nchw:
+        n, cin, h, w = x.shape
+    else:
+        n, h, w, cin = x.shape
+    if 2 * packed.numel() != lib().qcn_conv3x3_bf16_packed_size(cin, cout):
+        raise ValueError("conv3x3_bf16.packed: size does not match (cin, cout)")
+    oh, ow = (h // 2, w // 2) if pool else (h, w)
+    ydt = torch.bfloat16 if y_bf16 else torch.float32
+    if out is None:
+        out = torch.empty((n, cout, oh, ow) if y_nchw else (n, oh, ow, cout), dtype=ydt, device=x.device)
+    else:
+        _need(out, ydt, "conv3x3_bf16.out")
+    x_fmt = (_lib.QCN_FMT_BF16_NHWC if x.dtype == torch.bfloat16
+             else _lib.QCN_FMT_F32_NCHW if x_nchw else _lib.QCN_FMT_F32_NHWC)
+    y_fmt = _lib.QCN_FMT_BF16_NHWC if y_bf16 else _lib.QCN_FMT_F32_NCHW if y_nchw else _lib.QCN_FMT_F32_NHWC
+    alpha, beta = affine if affine is not None else (None, None)
+    check(lib().qcn_conv3x3_bf16(_ptr(x), n, h, w, cin, x_fmt, _ptr(packed), cout, _ptr(bias), _ptr(alpha),
+                                 _ptr(beta), int(bool(relu)), int(bool(pool)), y_fmt, _ptr(out), _stream()),
+          "conv3x3_bf16")
+    return out
+
+
 # ------------------------------- dynamic int8 conv pairs (DESIGN §25)
 class DynLayer(NamedTuple):
     """One layer of ``conv3x3_dyn_pair``: the weight, scale and epilogue

@@ -811,6 +811,49 @@ int qcn_conv3x3_dyn_pair32(const float* x, int nimg, int h, int w, int cin, int 
                            int pool, int y_nchw, float* y, float* y_stats, float* x_qparams, float* mid_qparams,
                            void* stream);
 
+/* ---- bf16 3x3 conv with fp32 accumulation ---------------------
+ * 3x3, stride 1, padding 1 on v_mfma_f32_16x16x32_bf16; fp32 or bf16 in and
+ * out, nothing calibrated, no range records:
+ *   xb  = bf16_rne(x)                    (identity when x is already bf16)
+ *   acc = sum over taps and ci of xb * wb   (fp32 accumulate from +0, order
+ *                                         fixed by the kernel, padding contributes +0)
+ *   t   = acc [+ bias[c]]; [t = fmaf(t, alpha[c], beta[c])]; [t = max(t, 0)]; [2x2 max]
+ *   y   = t as fp32, or bf16_rne(t) when y is bf16
+ * bf16_rne is round to nearest even; a product of two bf16 values is exact in
+ * fp32.  The order: Cin chunks of 8 G channels ascending (G = 8, 16, 32 for
+ * cout <= 64, <= 128, larger), one accumulator chain across them; inside a
+ * chunk one MFMA per 4 units of 8 channels of one tap, units tap-major,
+ * channel-group-minor.  It does not depend on nimg: an image's result is the
+ * same bits in any batch.  Rounding is monotone, so a bf16 y equals bf16_rne of
+ * the fp32 y, and a following qcn_conv3x3_bf16 gives the same bits from either.
+ * NaN, inf and magnitudes below 2^-126 are outside the contract. */
+#define QCN_FMT_F32_NHWC 0
+#define QCN_FMT_F32_NCHW 1
+#define QCN_FMT_BF16_NHWC 2
+/* Bytes of the packed weights (negative: a status). */
+int qcn_conv3x3_bf16_packed_size(int cin, int cout);
+/* Host packing of OIHW fp32 weights, rounded to bf16 (RNE), into the MFMA
+ * B-operand lane order in step order.  ng = ceil(cin / 8) channel groups run
+ * in chunks of G (above; ngc = the chunk's groups, G but for the last); a full
+ * chunk is F = 9 G / 4 steps of 4 units; 4 * ceil(cout / 64) column tiles ct:
+ *   out[((ct * steps + step) * 64 + lane) * 8 + b] = bf16_rne(w[co][ci][tap])
+ * co = 32 (ct / 2) + 2 (lane % 16) + ct % 2, chunk = step / F,
+ * u = 4 (step - F chunk) + lane / 16, tap = u / ngc = 3 ky + kx,
+ * ci = 8 G chunk + 8 (u % ngc) + b; +0 where tap > 8, ci >= cin or co >= cout.
+ * out: bf16 bit patterns, qcn_conv3x3_bf16_packed_size bytes. */
+int qcn_pack_conv3x3_weight_bf16(const float* w_oihw, int cout, int cin, uint16_t* out);
+/* x: x_fmt QCN_FMT_F32_NHWC [nimg][h][w][cin], QCN_FMT_F32_NCHW (torch's
+ * layout) or QCN_FMT_BF16_NHWC; y: y_fmt likewise ([h/2][w/2] maps with pool,
+ * h and w even), QCN_FMT_BF16_NHWC stores bf16_rne(t).  bias, alpha, beta may
+ * be NULL, alpha and beta only together.  Alignment: w_packed 16 bytes; fp32
+ * x, y 4 bytes; a bf16 x 16 bytes when cin % 8 == 0, else 2; a bf16 y 4 bytes
+ * when cout is even, else 2.  QCN_ERR_ARG for bad pointers, sizes, formats and
+ * alignment, QCN_ERR_UNSUPPORTED when x or y has more than 2^31 - 1 elements;
+ * both before any HIP call. */
+int qcn_conv3x3_bf16(const void* x, int nimg, int h, int w, int cin, int x_fmt, const uint16_t* w_packed,
+                     int cout, const float* bias, const float* alpha, const float* beta, int relu, int pool,
+                     int y_fmt, void* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
